@@ -13,6 +13,14 @@ value = uncompressed bytes round-tripped by all ranks / max-over-ranks wall time
 Default workload: BASELINE configs[1], 4096 x 4 KiB synthetic buffers per GPU (random / zero).
 
 usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1|dec64k|mixed|cfg3|...]
+                       [--dump-outputs DIR] [--full]
+
+A plain run does only what `value` needs: it builds the batch, warms up, times the K steps (issued
+eagerly, or replayed from one HIP graph with RLE_BENCH_GRAPH=1) and prints the result line.
+`--dump-outputs DIR` then writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+`--full` adds everything else the line can hold: the verified round trip, the same K steps in the
+other issue form (`value` is then the faster of the two), the per-kernel split and roofline, the
+two-stream figure, the dec64k north star and the CPU baseline.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N rank processes itself
 (127.0.0.1 rendezvous) before anything touches the GPU; under torch.distributed.run each rank
@@ -333,6 +341,53 @@ def load_pmc(workload):
         return None
 
 
+# ------------------------------------------------------------------------------------ the outputs
+DUMP_SEED = 0x5EED
+DUMP_DEC_VALUES = 8_000_000   # float32 values of decoded bytes (32 MB) ...
+DUMP_ENC_VALUES = 6_000_000   # ... and of compressed bytes (24 MB); with the per-buffer vectors < 64 MB
+
+
+def _sample(total, limit, rng, dev):
+    """Every index of [0, total) when there are at most `limit`, else `limit` of them drawn once from
+    the seeded generator (sorted); the same arguments give the same indices in every run."""
+    import numpy as np
+    if total <= limit:
+        return torch.arange(total, dtype=torch.int64, device=dev)
+    idx = np.unique(rng.integers(0, total, size=limit, dtype=np.int64))
+    return torch.from_numpy(idx).to(dev)
+
+
+def dump_outputs(B, slot, out_dir, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as
+    out_dir/<name>.npy (one rank; <name>_rank<r>.npy at N > 1):
+      clen     float64[n]  the compressed size of every buffer (encode's out_len)
+      status   float64[n]  the status word of every buffer (the decode's, written last)
+      encoded  float32[k]  compressed bytes: a fixed seeded sample of the compressed arena's
+                           positions (all of them when they fit), 0 where a position lies past its
+                           buffer's compressed size (the slots keep their worst-case capacity and the
+                           codec writes nothing there)
+      decoded  float32[k]  decoded bytes: the same kind of sample of the decoded arena
+    The synthetic inputs are generated from the buffers' global indices alone, so two builds run with
+    the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(DUMP_SEED)
+    dev = B.d_out.device
+    clen = B.clens[slot]
+    # the byte positions [coffs[i], coffs[i] + clen[i]) hold buffer i's stream
+    ci = _sample(B.d_c.numel(), DUMP_ENC_VALUES // world, rng, dev)
+    owner = torch.bucketize(ci, B.coffs, right=True) - 1
+    enc = torch.where(ci - B.coffs[owner] < clen[owner], B.d_c[ci], torch.zeros((), dtype=torch.uint8, device=dev))
+    di = _sample(B.d_out.numel(), DUMP_DEC_VALUES // world, rng, dev)
+    arrays = {"clen": clen.to(torch.float64), "status": B.status.to(torch.float64),
+              "encoded": enc.to(torch.float32), "decoded": B.d_out[di].to(torch.float32)}
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), t.cpu().numpy())
+    return sorted(arrays)
+
+
 # ------------------------------------------------------------------------------------ the exchange
 # The exchange mode (VERDICT r3 item 7): "auto" times inline and async on the job's own ranks and keeps the faster.
 XMODE_REASON = ("auto: inline and async timed on the job's own ranks before the timed region, the faster kept "
@@ -535,12 +590,15 @@ def run_rank(args):
 
     B.encode(stream)
     B.calibrate()
-    # verified on one step first, so that the W warmup steps run right before the timed region (host
-    # work between them, with the GPU idle, made the first timed step ~50 us slower: tools/step_profile.py)
-    loop.one_step(0)
-    sync(dry)
-    ok = B.verify()
-    offsets_ok = xch.verify(stream) if xch is not None else None
+    # --full, and the exchange's offsets at N > 1: verified on one step first, so that the W warmup
+    # steps run right before the timed region (host work between them, with the GPU idle, made the
+    # first timed step ~50 us slower: tools/step_profile.py)
+    ok = offsets_ok = None
+    if args.full or xch is not None:
+        loop.one_step(0)
+        sync(dry)
+        ok = B.verify() if args.full else None
+        offsets_ok = xch.verify(stream) if xch is not None else None
     c_bytes = int(B.clen.sum().item())
     u_local = B.u_bytes
     # the graph (N > 1) is captured here, outside the timed region, and replayed for warmup too
@@ -618,7 +676,12 @@ def run_rank(args):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     loop_gpu_s = ev[0].elapsed_time(ev[1]) * 1e-3 if ev else None
-    if not dry and not timed_ev:
+    dumped = None
+    if args.dump_outputs and not dry:   # (before anything below reuses the batch's buffers)
+        dumped = dump_outputs(B, (args.steps - 1) % 2, args.dump_outputs, rank, world)
+    elif args.dump_outputs and rank == 0:
+        print("bench: --dry-run launches no codec, nothing to dump", file=sys.stderr)
+    if args.full and not dry and not timed_ev:
         loop.steps(max(1, args.warmup))
         sync(dry)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -633,7 +696,7 @@ def run_rank(args):
         elapsed = float(t.item())
         okt = torch.tensor([1 if ok else 0, 1 if offsets_ok else 0], dtype=torch.int32, device=dev)
         dist.all_reduce(okt, op=dist.ReduceOp.MIN)
-        ok = None if dry else bool(okt[0].item())
+        ok = bool(okt[0].item()) if args.full and not dry else None
         offsets_ok = bool(okt[1].item())
         ut = torch.tensor([u_local], dtype=torch.int64, device=dev)
         dist.all_reduce(ut, op=dist.ReduceOp.SUM)
@@ -645,7 +708,7 @@ def run_rank(args):
     # one HIP graph when the headline issued them eagerly, or eagerly when it replayed a graph
     # (VERDICT r4 item 7, r5 item 3), so the launch share is visible beside the headline
     other = None
-    if xch is None and not dry:
+    if args.full and xch is None and not dry:
         was_plain = loop.plain
         try:
             if not was_plain:
@@ -675,7 +738,7 @@ def run_rank(args):
     headline_graph = loop.plain != use_other
 
     kern = roofline = conc = north = cpu = None
-    if not dry:
+    if args.full and not dry:
         kern, roofline = measure_kernels(B, args, stream, u_local, c_bytes, loop_gpu_s,
                                          "timed_loop_events" if timed_ev else "rerun_events")
         if rank == 0 and not multi:
@@ -706,7 +769,10 @@ def run_rank(args):
                "verified_bit_exact_roundtrip": ok, "host_wait": sched,
                "issue": ("one HIP graph of the K timed steps (captured before the timed region), replayed"
                          if headline_graph else "eager: 2 launches per step from the host")
-                        + " (the faster of the two issue forms, each timed over the same K steps)",
+                        + (" (the faster of the two issue forms, each timed over the same K steps)" if other
+                           else " (the only issue form timed; --full times the other one as well)"
+                           if xch is None and not dry else ""),
+               "full": args.full, "outputs_dumped": dumped,
                "timed_region_events": timed_ev,
                "value_eager": eager["value"] if eager else (round(primary["value"], 3) if not loop.plain else None),
                "ms_per_step_eager": eager["ms_per_step"] if eager else (round(primary["ms_per_step"], 4) if not loop.plain else None),
@@ -851,12 +917,17 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="cfg1", choices=sorted(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: verify the round trip, time the other issue form, the per-kernel "
+                         "split and roofline, the two-stream figure, the dec64k north star and the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-north-star", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-north-star", action="store_true", help="--full without the dec64k north star")
     ap.add_argument("--no-concurrent", action="store_true",
-                    help="skip the informational two-stream figure (profiling runs: its overlapped launches "
-                         "would enter the per-kernel averages)")
+                    help="--full without the informational two-stream figure (profiling runs: its overlapped "
+                         "launches would enter the per-kernel averages)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU / gloo rehearsal of the rank loop without codec launches (tests)")
     return ap.parse_args(argv)

@@ -132,8 +132,8 @@ def test_bench_exchange_path_one_rank(xmode):
     env = dict(os.environ, RLE_BENCH_FORCE_EXCHANGE="1", RLE_BENCH_XMODE=xmode)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--no-cpu",
-                        "--no-north-star", "--no-concurrent"], env=env, capture_output=True, text=True, timeout=110)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--full",
+                        "--no-cpu", "--no-north-star", "--no-concurrent"], env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["verified_bit_exact_roundtrip"] is True

@@ -5,9 +5,9 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-benv}; ENVS=$2; mkdir -p $O
 for rep in 1 2 3; do
   for E in $ENVS; do
     if [ "$E" = "-" ]; then
-      timeout -k 10 300 python3 $R/bench.py --no-cpu --no-north-star --steps 50 > $O/run.json 2>>$O/err.log || exit $?
+      timeout -k 10 300 python3 $R/bench.py --full --no-cpu --no-north-star --steps 50 > $O/run.json 2>>$O/err.log || exit $?
     else
-      env "$E" timeout -k 10 300 python3 $R/bench.py --no-cpu --no-north-star --steps 50 > $O/run.json 2>>$O/err.log || exit $?
+      env "$E" timeout -k 10 300 python3 $R/bench.py --full --no-cpu --no-north-star --steps 50 > $O/run.json 2>>$O/err.log || exit $?
     fi
     python3 -c "
 import json; d=json.loads(open('$O/run.json').read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ case $rc in 124|134|137|139) exit $rc;; esac
 timeout -k 10 300 python -u -m pytest $R/tests/test_e2e_server.py -m gpu -s -q --timeout 240 --timeout-method thread > $O/e2e.log 2>&1
 rc=$?; echo "e2e rc=$rc" >> $O/status
 case $rc in 124|134|137|139) exit $rc;; esac
-timeout -k 10 400 python $R/bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python $R/bench.py --full > $O/bench.json 2> $O/bench.err
 rc=$?; echo "bench rc=$rc" >> $O/status
 case $rc in 124|134|137|139) exit $rc;; esac
 timeout -k 10 300 python $R/tools/hostpath_bench.py > $O/hostpath.json 2> $O/hostpath.err
@@ -23,7 +23,7 @@ timeout -k 10 500 python -u $R/tools/roofline_sweep.py > $O/sweep.json 2> $O/swe
 rc=$?; echo "sweep rc=$rc" >> $O/status
 case $rc in 124|134|137|139) exit $rc;; esac
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --steps 20 --no-cpu --no-concurrent > $O/prof.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --full --steps 20 --no-cpu --no-concurrent > $O/prof.log 2>&1
 rc=$?; echo "prof rc=$rc" >> $O/status
 case $rc in 124|134|137|139) exit $rc;; esac
 for WL in cfg1 dec64k; do

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Turn one GPU round's raw rocprofv3 output (tools/gpu_round.sh) into the committed profiles/:
 
-  profiles/<tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary of `bench.py --steps 20`
+  profiles/<tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary of `bench.py --full --steps 20`
   profiles/<tag>_kernel_split.md    the same trace split per (kernel, grid): bench runs the cfg1 batch
                                     and then the dec64k north-star batch, which the stats file mixes
   profiles/<tag>_pmc.md             FETCH_SIZE / WRITE_SIZE per codec launch for each workload
@@ -70,7 +70,7 @@ def main():
                     os.path.join(PROF, f"{tag}_kernel_stats.csv"))
     table, _ = kernel_split(src)
     with open(os.path.join(PROF, f"{tag}_kernel_split.md"), "w") as f:
-        f.write(f"# {tag}: rocprofv3 --kernel-trace of `python3 bench.py --steps 20 --no-cpu`\n\n"
+        f.write(f"# {tag}: rocprofv3 --kernel-trace of `python3 bench.py --full --steps 20 --no-cpu`\n\n"
                 "Split per (kernel, grid). The smaller grids are the configs[1] batch (4096 x 4 KiB),\n"
                 "the larger ones the dec64k north-star batch (16384 x 64 KiB); bench.py times both.\n\n")
         f.write(table + "\n")
