@@ -11,6 +11,7 @@ Outputs (tests/golden/):
                     (sha256 of input and of compressed output), invalid-stream decodes
   dummyfiles.json   U, C, sha256 pins of every file in the reference's tests/dummyFiles
   dummyFiles/…      a few small fixture files copied as data (inputs of the reference's tests)
+  stream_family.json  sha256 pins of the reference's decodes of tests/stream_family.py's cases
 """
 import ctypes
 import hashlib
@@ -170,6 +171,31 @@ def main():
         json.dump(D, f, indent=1)
     print("vectors:", {k: len(v) for k, v in V.items() if isinstance(v, list)},
           "files:", len(D["files"]), "test2:", D["test2_max_storage"])
+    stream_family_pins()
+
+
+def stream_family_pins():
+    """stream_family.json: for every probe position of tests/stream_family.py one sha256 over
+    stream | U | the compiled reference's output of every case at that position.  A position's
+    cases depend on the position alone, so the decode forms whose edge sets share a position share
+    its pin.  The reference runs with E = C + 16 (with E = 0 it would write outside its block when
+    the stream decodes past U); a cap = U case pins the first U bytes of that output."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import stream_family as F
+    P = {"source": "reference src/rleCompression.c compiled unchanged (-Wall -g -std=c99)", "positions": {}}
+    h = hashlib.sha256()
+    for c in F.family(F.TILE):
+        h.update(c.stream + c.U.to_bytes(8, "little") + c.cap.to_bytes(8, "little"))
+    P["family_%d" % F.TILE] = h.hexdigest()
+    ncases = 0
+    for p in F.all_positions():
+        fam = F.family(p)
+        outs = [ref_decompress(c.stream, c.U, len(c.stream) + 16)[:c.cap] for c in fam]
+        P["positions"][str(p)] = F.pin(fam, outs)
+        ncases += len(fam)
+    with open(os.path.join(HERE, "stream_family.json"), "w") as f:
+        json.dump(P, f, indent=0)
+    print("stream family:", len(P["positions"]), "positions,", ncases, "cases")
 
 
 if __name__ == "__main__":

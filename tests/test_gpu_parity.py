@@ -26,17 +26,38 @@ def _i64(vals):
     return torch.tensor(np.asarray(vals, dtype=np.int64), device=DEV)
 
 
-def gpu_encode(bufs, seg=False, max_len=None, flags=0, one_pass=False):
+def _input_image(bufs, pad):
+    """The input image of a launch: (offsets, host array).  pad=None: packed 16-byte-aligned slots in
+    a zeroed image.  pad=k: k spare bytes after every slot, and every byte outside the buffers
+    hostile instead of zero: after each buffer the bytes last, last, '9', last, last, '9', ...
+    (last: the buffer's final byte), so a decoder that read memory past its length would see a pair
+    token and an encoder would see its final run go on.  The device API ignores those bytes: they
+    read as 0x00 (include/rleCompression.h:17-18)."""
+    sizes = [len(b) for b in bufs]
+    if pad is None:
+        offs, total = R.layout(sizes)
+        host = np.zeros(total, np.uint8)
+    else:
+        offs, total = R.layout(sizes, pad=pad)
+        total += 64
+        host = np.empty(total, np.uint8)
+        host[:offs[0] if offs else total] = 0x39
+    for b, o, e in zip(bufs, offs, list(offs[1:]) + [total]):
+        host[o:o + len(b)] = np.frombuffer(b, np.uint8)
+        if pad is not None:
+            last = b[-1] if b else 0x61
+            host[o + len(b):e] = np.resize(np.array([last, last, 0x39], np.uint8), e - o - len(b))
+    return offs, host
+
+
+def gpu_encode(bufs, seg=False, max_len=None, flags=0, one_pass=False, pad=None):
     """Encode a list of byte strings in ONE batched launch (seg: the segmented multi-wave form;
     max_len: the sized entry point with that hint, which picks the cooperative kernels for small
-    buffers; one_pass: a workgroup per buffer in rounds, rle_encode_stream_launch); returns
-    (outputs, status)."""
+    buffers; one_pass: a workgroup per buffer in rounds, rle_encode_stream_launch; pad: hostile
+    bytes around the input slots, _input_image); returns (outputs, status)."""
     n = len(bufs)
     sizes = [len(b) for b in bufs]
-    in_offs, in_total = R.layout(sizes)
-    host = np.zeros(in_total, np.uint8)
-    for b, o in zip(bufs, in_offs):
-        host[o:o + len(b)] = np.frombuffer(b, np.uint8)
+    in_offs, host = _input_image(bufs, pad)
     out_offs, out_total = R.compressed_slots(sizes)
     d_in = torch.from_numpy(host).to(DEV)
     d_out = torch.full((out_total + 16,), POISON, dtype=torch.uint8, device=DEV)
@@ -62,13 +83,11 @@ def gpu_encode(bufs, seg=False, max_len=None, flags=0, one_pass=False):
     return res, status.cpu().numpy()
 
 
-def gpu_decode(streams, usizes, caps=None, poison=True, seg=False, max_in_len=None, max_out_len=None, flags=0):
+def gpu_decode(streams, usizes, caps=None, poison=True, seg=False, max_in_len=None, max_out_len=None, flags=0,
+               pad=None):
     n = len(streams)
     caps = caps if caps is not None else list(usizes)
-    in_offs, in_total = R.layout([len(s) for s in streams])
-    host = np.zeros(in_total, np.uint8)
-    for s, o in zip(streams, in_offs):
-        host[o:o + len(s)] = np.frombuffer(s, np.uint8)
+    in_offs, host = _input_image(streams, pad)
     out_offs, out_total = R.layout(caps)
     d_in = torch.from_numpy(host).to(DEV)
     d_out = torch.full((out_total + 16,), POISON if poison else 0, dtype=torch.uint8, device=DEV)
