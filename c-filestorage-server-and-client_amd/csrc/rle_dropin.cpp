@@ -7,7 +7,8 @@
 // Each calling thread (the server's worker pool, src/server.c:520-524) gets its own HIP stream,
 // pinned host buffers and device buffers, created lazily on its first call (there is no init
 // hook in the server, src/server.c:406-524) and released at thread exit.  A call is one batched
-// kernel launch with B = 1 plus the host<->device traffic, sized to the call:
+// kernel launch with B = 1 plus the host<->device traffic, sized to the call (the size classes, their
+// thresholds and the settings that move them are defined in rle_route.h, one function per entry point):
 //   small (one wave walks it)  zero-copy on the thread's mapped pinned buffer, one launch, one sync;
 //   medium (up to 256 KiB)     zero-copy too: cooperative or segmented kernels on the mapped buffer;
 //   large                      the caller's buffer and the result block registered for the call, one
@@ -42,7 +43,7 @@
 #include "rle_mi355x.h"
 #include "rle_service.h"
 #include "rle_build.h"
-#include "rle_coop_limits.h"
+#include "rle_route.h"
 
 // Measured-slower host-path variants (call coalescing, pipelined staging) are compiled only into the
 // test library (build/librle_mi355x_testhooks.so) and `make variant` builds, never into the product
@@ -65,6 +66,25 @@ struct Stats {
     std::atomic<uint64_t> ns_stage_in{0}, ns_device{0}, ns_stage_out{0};
     std::atomic<uint64_t> calls_coalesced{0}, launches_coalesced{0};   // zero-copy calls / their combined launches
     std::atomic<uint64_t> calls_registered{0}, calls_reg_fallback{0};  // registered large calls / staged instead
+
+    // One finished call of a kind (RLEdecompressN: n of them): caller bytes in / out, bytes moved each
+    // way, wall time per phase (a call without staging phases of its own: all device time).
+    struct Call {
+        uint64_t in, out, h2d, d2h, ns_stage_in, ns_device, ns_stage_out;
+    };
+    void compress(const Call& k) { add(calls_compress, 1, k); }
+    void decompress(const Call& k, uint64_t n = 1) { add(calls_decompress, n, k); }
+    void append(const Call& k) { add(calls_append, 1, k); }
+    void add(std::atomic<uint64_t>& calls, uint64_t n, const Call& k) {
+        calls += n;
+        bytes_in += k.in;
+        bytes_out += k.out;
+        bytes_h2d += k.h2d;
+        bytes_d2h += k.d2h;
+        if (k.ns_stage_in) ns_stage_in += k.ns_stage_in;
+        ns_device += k.ns_device;
+        if (k.ns_stage_out) ns_stage_out += k.ns_stage_out;
+    }
 } g_stats;
 inline uint64_t now_ns() {
     return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -115,13 +135,11 @@ bool too_big(const char* who, size_t n) {
     return true;
 }
 
-// Small-call threshold: up to this many input bytes the worst-case output is copied back in the
-// same round trip as its size (one stream sync instead of two).
-constexpr size_t kOneTripBytes = 128u << 10;
-// From these sizes one call is cut into segments processed by separate waves
-// (rle_*_batch_device_seg) instead of one wave walking the whole buffer.
-constexpr size_t kSegEncodeBytes = 48u << 10;
-constexpr size_t kSegDecodeBytes = 32u << 10;
+// The size classes and the settings that select a call's path (rle_route.h); init_once fills them.
+using rle::kZcIn;
+using rle::kZcOut;
+using rle::Body;
+rle::Settings g_set;
 
 // Host<->device transfers of large calls, selected by RLE_MI355X_STAGING:
 //   direct (default) the HIP runtime copies from / to the caller's pageable memory itself;
@@ -135,14 +153,6 @@ Staging g_staging = Staging::Direct;
 constexpr size_t kPipeMinBytes = 256u << 10;
 constexpr int kPipeEvents = 16;
 
-// Small calls run zero-copy by default: the kernel reads the caller's bytes from, and writes its
-// result into, this thread's mapped pinned buffer over PCIe, with no copy commands at all (4 KiB:
-// 19 / 20 us per compress / decompress call against 21 / 23 with one H2D + one D2H;
-// profiles/r1e_small.md).  RLE_MI355X_SMALL=copy selects the copying form.
-bool g_zerocopy = true;
-#if RLE_VARIANTS
-bool g_coalesce = false;   // concurrent zero-copy calls join one launch (submit); RLE_MI355X_COALESCE=1: on
-#endif
 size_t g_presize = 1u << 20;   // staging allocated with each thread context (presize); RLE_MI355X_PRESIZE
 // Zero-copy calls learn of their completion from the status word the kernel stores last, behind a
 // system-scope release of its output (RLE_LAUNCH_STATUS_FLAG), by polling it in the mapped buffer
@@ -152,34 +162,11 @@ bool g_poll = true;
 // How long a completion poll spins (pause) before it yields the core between reads:
 // RLE_MI355X_SPIN_NS (default 50 us, about the longest small call).
 uint64_t g_spin_ns = 50000;
-// Small calls through the resident service (rle_service.h) instead of a launch each:
-// RLE_MI355X_SERVICE=1, in the RLE_VARIANTS test library only (measured slower, round 5).
-bool g_service = false;
-// Zero-copy calls from this many bytes (encode: U, decode: C) run the segmented kernels on the mapped
-// buffer instead of one wave walking it, and the zero-copy form then takes calls up to 256 KiB in
-// (RLE_MI355X_ZC_SEG=<bytes>; 0 = never).  profiles/r4f_callrate_zcseg.txt, µs per call on 1 / 8
-// threads: 40 KB 42.2 / 91.7 against 66.1 / 151.3 for one wave over the mapped buffer; 24 KiB
-// 41.2 / 91.1 against 34.8 / 64.2 (the five launches cost more than a short walk).
-size_t g_zc_seg = 32u << 10;
-// ... except the calls one cooperative workgroup takes (rle_coop_limits.h: encode up to 64 KiB,
-// decode up to 80 tiles decoding to 64 KiB; rounds of 16 waves, one launch, polled like the smaller
-// calls).  RLE_MI355X_ZC_COOP=0: the segmented kernels from g_zc_seg as before (round 5 A/B).
-bool g_zc_coop = true;
-// Input up to 256 KiB, output up to 384 KiB (r5n / r5o, profiles/r5o_zc_size.md: past the cooperative
-// kernels' reach the segmented kernels on the mapped buffer beat the two copies of the staged path up
-// to 256 KiB, e.g. a 96 KiB compress 43 against 68 us; 80 KiB of input until round 5's r5n)
-#ifndef RLE_ZC_IN_KIB
-#define RLE_ZC_IN_KIB 256
-#endif
-constexpr size_t kZcIn = 0, kZcWords = (size_t)RLE_ZC_IN_KIB << 10, kZcOut = kZcWords + (4u << 10),
-                 kZcBytes = kZcOut + (kZcWords * 3 / 2 > (204u << 10) ? kZcWords * 3 / 2 : (204u << 10));
-static_assert(kZcWords >= rle::kCoopDecMaxIn, "zero-copy input region");
-constexpr size_t kZcMaxIn = kZcWords, kZcMaxOut = kZcBytes - kZcOut;   // one zero-copy call's bytes
 
 // Registered large calls (profiles/r6j_hostpath_reg.txt, r6_hostpath.md): from
-// g_reg_min bytes (RLE_MI355X_REG_MIN; 0 = never; by default the sizes past the zero-copy calls'
-// reach) an RLEcompress / RLEdecompress registers the caller's input and the result block with the
-// runtime for the duration of the call (hipHostRegister + unregister of 1 MiB of touched heap
+// g_set.reg_min bytes (rle_route.h: RLE_MI355X_REG_MIN; 0 = never; by default the sizes past the
+// zero-copy calls' reach) an RLEcompress / RLEdecompress registers the caller's input and the result
+// block with the runtime for the duration of the call (hipHostRegister + unregister of 1 MiB of touched heap
 // memory: 0.9 + 0.3 µs).  The input travels by one DMA straight from the caller's pages, the kernels
 // work in device memory, and a copy kernel stores the result into the registered block over PCIe
 // (the write pass storing there itself measured slower: its partial lines, r6k): no CPU copy either
@@ -194,7 +181,6 @@ constexpr size_t kZcMaxIn = kZcWords, kZcMaxOut = kZcBytes - kZcOut;   // one ze
 // with the count of large calls in flight (no registration starts while another large call is in
 // flight), and a transfer whose caller pages meet a live registration's pages goes through the
 // pinned staging, never handing the runtime that pointer (live_pages).
-size_t g_reg_min = kZcMaxIn + 1;   // (past the zero-copy calls: r6m / r6o)
 std::mutex g_reg_mu;
 std::atomic<int> g_large_calls{0};       // large calls in flight (changed under g_reg_mu)
 // ... and when two last overlapped: a call registers only when none has overlapped it for
@@ -418,18 +404,19 @@ void init_once() {
     if (const char* e = getenv("RLE_MI355X_FAKE_DEVICES")) g_fake_devs = atoi(e) > 0 ? atoi(e) : 0;
     if (const char* e = getenv("RLE_MI355X_FAKE_DELAY_US")) g_fake_delay_us = (unsigned)atoi(e);
 #endif
+    g_set.fake_devs = g_fake_devs;
     if (g_fake_devs) g_ndev = g_fake_devs;
     else if (hipGetDeviceCount(&g_ndev) != hipSuccess) g_ndev = 0;
     if (const char* e = getenv("RLE_MI355X_DEVICE")) g_dev_pin = atoi(e);
-    if (const char* e = getenv("RLE_MI355X_SMALL")) g_zerocopy = strcmp(e, "copy") != 0;
+    if (const char* e = getenv("RLE_MI355X_SMALL")) g_set.zerocopy = strcmp(e, "copy") != 0;
     if (const char* e = getenv("RLE_MI355X_POLL")) g_poll = strcmp(e, "0") != 0;
     if (const char* e = getenv("RLE_MI355X_SPIN_NS")) g_spin_ns = strtoull(e, nullptr, 10);
-    if (const char* e = getenv("RLE_MI355X_SERVICE")) g_service = strcmp(e, "0") != 0;
-    if (const char* e = getenv("RLE_MI355X_ZC_SEG")) g_zc_seg = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("RLE_MI355X_ZC_COOP")) g_zc_coop = strcmp(e, "0") != 0;
-    if (const char* e = getenv("RLE_MI355X_COOP")) g_zc_coop = g_zc_coop && strcmp(e, "0") != 0;   // (no workgroups to take them)
+    if (const char* e = getenv("RLE_MI355X_SERVICE")) g_set.service = strcmp(e, "0") != 0;
+    if (const char* e = getenv("RLE_MI355X_ZC_SEG")) g_set.zc_seg = (size_t)strtoull(e, nullptr, 10);
+    if (const char* e = getenv("RLE_MI355X_ZC_COOP")) g_set.zc_coop = strcmp(e, "0") != 0;
+    if (const char* e = getenv("RLE_MI355X_COOP")) g_set.zc_coop = g_set.zc_coop && strcmp(e, "0") != 0;   // (no workgroups to take them)
 #if RLE_VARIANTS
-    if (const char* e = getenv("RLE_MI355X_COALESCE")) g_coalesce = strcmp(e, "0") != 0;
+    if (const char* e = getenv("RLE_MI355X_COALESCE")) g_set.coalesce = strcmp(e, "0") != 0;
 #endif
     if (const char* e = getenv("RLE_MI355X_PRESIZE")) g_presize = (size_t)strtoull(e, nullptr, 10);
     if (const char* e = getenv("RLE_MI355X_STAGING")) {
@@ -439,7 +426,7 @@ void init_once() {
 #if RLE_TEST_HOOKS
     if (const char* e = getenv("RLE_MI355X_FAIL_ALLOC_ABOVE")) g_fail_above = (size_t)strtoull(e, nullptr, 10);
 #endif
-    if (const char* e = getenv("RLE_MI355X_REG_MIN")) g_reg_min = (size_t)strtoull(e, nullptr, 10);
+    if (const char* e = getenv("RLE_MI355X_REG_MIN")) g_set.reg_min = (size_t)strtoull(e, nullptr, 10);
     if (const char* e = getenv("RLE_MI355X_REG_QUIET_US")) g_reg_quiet_ns = 1000ull * strtoull(e, nullptr, 10);
     if (const char* e = getenv("RLE_MI355X_STAGE_CAP")) {
         const long long v = atoll(e);
@@ -738,41 +725,35 @@ void drain_after_oom() {
 // Staging and device buffers grow on demand (never below 16 bytes, so a launch never sees NULL).
 // A failed allocation throws std::bad_alloc, which each entry point turns into the reference's
 // allocation-failure result (NULL, or -1 with errno = ENOMEM) instead of aborting the server.
-void grow_host(uint8_t*& p, size_t& cap, size_t need) {
+void grow(uint8_t*& p, size_t& cap, size_t need, bool host) {   // (pinned host memory, or device memory)
     need = std::max<size_t>(need, 16);
     if (need <= cap) return;
     size_t n = cap ? cap : (64u << 10);
     while (n < need) n *= 2;
-    if (p) check(hipHostFree(p), "hipHostFree");
+    if (p) check(host ? hipHostFree(p) : hipFree(p), host ? "hipHostFree" : "hipFree");
     p = nullptr;
     cap = 0;
-    if (injected_failure(n) || hipHostMalloc(reinterpret_cast<void**>(&p), n, hipHostMallocDefault) != hipSuccess) {
+    void** q = reinterpret_cast<void**>(&p);
+    if (injected_failure(n) || (host ? hipHostMalloc(q, n, hipHostMallocDefault) : hipMalloc(q, n)) != hipSuccess) {
         (void)hipGetLastError();
         p = nullptr;
         throw std::bad_alloc();
     }
     cap = n;
 }
-void grow_dev(uint8_t*& p, size_t& cap, size_t need) {
-    need = std::max<size_t>(need, 16);
-    if (need <= cap) return;
-    size_t n = cap ? cap : (64u << 10);
-    while (n < need) n *= 2;
-    if (p) check(hipFree(p), "hipFree");
-    p = nullptr;
-    cap = 0;
-    if (injected_failure(n) || hipMalloc(reinterpret_cast<void**>(&p), n) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        throw std::bad_alloc();
-    }
-    cap = n;
+inline void grow_host(uint8_t*& p, size_t& cap, size_t need) { grow(p, cap, need, true); }
+inline void grow_dev(uint8_t*& p, size_t& cap, size_t need) { grow(p, cap, need, false); }
+// The staging of a call that copies in bytes in and out bytes back: pinned and device, both ways.
+void grow_staging(Ctx* c, size_t in, size_t out) {
+    grow_host(c->h_in, c->h_in_cap, in);
+    grow_host(c->h_out, c->h_out_cap, out);
+    grow_dev(c->d_in, c->d_in_cap, in);
+    grow_dev(c->d_out, c->d_out_cap, out);
 }
-
-
-}  // namespace
-
-namespace {
+// A kernel launch's return code: an error ends the process, as a failed HIP call does (check).
+inline void launched(int rc, const char* what) {
+    if (rc != RLE_OK) die(what, hipGetLastError());
+}
 
 // An encode whose status is not OK has no trustworthy output (RLE_STATUS_INTERNAL: the segmented
 // kernels' carry wait ran out; never expected): the call fails loudly rather than return it.
@@ -784,9 +765,10 @@ void check_encode_status(uint32_t st) {
 }
 
 // Queues on c->s the encode of n device bytes at d_src (16-byte aligned) into c->d_out, the D2H of
-// C into h_meta[kMetaEnc + 3] and, up to kOneTripBytes, of the worst-case output into h_out (one
-// stream sync per call).  Returns whether the output travels with its size.
+// C into h_meta[kMetaEnc + 3] and, where the form is one-trip, of the worst-case output into h_out
+// (one stream sync per call).  Returns whether the output travels with its size.
 bool queue_encode(Ctx* c, const uint8_t* d_src, size_t n) {
+    const rle::DeviceForm form = rle::encode_form(n);
     const size_t maxC = rle_max_compressed_size(n);
     grow_dev(c->d_out, c->d_out_cap, round16(maxC));
     uint64_t* hm = c->h_meta + kMetaEnc;
@@ -794,19 +776,17 @@ bool queue_encode(Ctx* c, const uint8_t* d_src, size_t n) {
     hm[0] = 0; hm[1] = n; hm[2] = 0; hm[3] = 0;
     check(hipMemcpyAsync(dm, hm, 4 * sizeof(uint64_t), hipMemcpyHostToDevice, c->s), "H2D(meta)");
     uint32_t* d_status = reinterpret_cast<uint32_t*>(dm + 5);
-    if (n >= kSegEncodeBytes) grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, n));
-    const int erc = n >= kSegEncodeBytes
-                        ? rle_encode_batch_device_seg(d_src, dm + 0, dm + 1, c->d_out, dm + 2, dm + 3, d_status, 1, n,
-                                                      c->d_ws, c->d_ws_cap, c->s)
-                        : rle_encode_batch_device_sized(d_src, dm + 0, dm + 1, c->d_out, dm + 2, dm + 3, d_status, 1, n, c->s);
-    if (erc != RLE_OK) die("encode launch", hipGetLastError());
+    if (form.seg) grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, n));
+    launched(form.seg ? rle_encode_batch_device_seg(d_src, dm + 0, dm + 1, c->d_out, dm + 2, dm + 3, d_status, 1, n,
+                                                    c->d_ws, c->d_ws_cap, c->s)
+                      : rle_encode_batch_device_sized(d_src, dm + 0, dm + 1, c->d_out, dm + 2, dm + 3, d_status, 1, n,
+                                                      c->s), "encode launch");
     check(hipMemcpyAsync(hm + 3, dm + 3, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->s), "D2H(meta)");
-    const bool one_trip = n <= kOneTripBytes;
-    if (one_trip) {
+    if (form.one_trip) {
         grow_host(c->h_out, c->h_out_cap, maxC);
         check(hipMemcpyAsync(c->h_out, c->d_out, maxC, hipMemcpyDeviceToHost, c->s), "D2H");
     }
-    return one_trip;
+    return form.one_trip;
 }
 
 // After the stream sync that follows queue_encode: makes encoded bytes [from, C) present in h_out
@@ -822,9 +802,9 @@ size_t fetch_encoded(Ctx* c, bool one_trip, size_t from) {
     return C;
 }
 
-// The caller's block: head[0, headLen) ‖ h_out[from, C) ‖ 16 zero bytes (the reference's calloc'd
+// The caller's block: head[0, headLen) ‖ src[from, C) ‖ 16 zero bytes (the reference's calloc'd
 // block ends in zeros that decoders read past C).  NULL on allocation failure; *outC always set.
-char* make_block_from(const uint8_t* src, const char* head, size_t headLen, size_t from, size_t C, size_t* outC) {
+char* make_block(const uint8_t* src, const char* head, size_t headLen, size_t from, size_t C, size_t* outC) {
     const size_t total = headLen + (C - from);
     *outC = total;
     char* r = static_cast<char*>(malloc(total + 16));
@@ -834,8 +814,16 @@ char* make_block_from(const uint8_t* src, const char* head, size_t headLen, size
     memset(r + total, 0, 16);
     return r;
 }
-char* make_block(const Ctx* c, const char* head, size_t headLen, size_t from, size_t C, size_t* outC) {
-    return make_block_from(c->h_out, head, headLen, from, C, outC);
+
+// Launches the decode of one buffer, its record (6 words, the status last) at device address dw: the
+// segmented kernels (d_ws grown beforehand) or one wave.
+void launch_decode(Ctx* c, bool seg, const uint8_t* d_src, uint8_t* d_dst, uint64_t* dw, size_t C, size_t U) {
+    uint32_t* d_status = reinterpret_cast<uint32_t*>(dw + 5);
+    launched(seg ? rle_decode_batch_device_seg(d_src, dw + 0, dw + 1, d_dst, dw + 2, dw + 3, dw + 4, d_status, 1, C,
+                                               c->d_ws, c->d_ws_cap, c->s)
+                 : rle_decode_batch_device_sized(d_src, dw + 0, dw + 1, d_dst, dw + 2, dw + 3, dw + 4, d_status, 1, C, U,
+                                                 c->s),
+             "decode launch");
 }
 
 // Queues the decode of C device bytes at d_src into d_dst (U decoded bytes, slot of cap bytes) and
@@ -845,14 +833,9 @@ void queue_decode(Ctx* c, const uint8_t* d_src, size_t C, uint8_t* d_dst, size_t
     uint64_t* dm = c->d_meta + kMetaDec;
     hm[0] = 0; hm[1] = C; hm[2] = 0; hm[3] = U; hm[4] = cap; hm[5] = 0;
     check(hipMemcpyAsync(dm, hm, 6 * sizeof(uint64_t), hipMemcpyHostToDevice, c->s), "H2D(meta)");
-    uint32_t* d_status = reinterpret_cast<uint32_t*>(dm + 5);
-    if (C >= kSegDecodeBytes) grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, C));
-    const int drc = C >= kSegDecodeBytes
-                        ? rle_decode_batch_device_seg(d_src, dm + 0, dm + 1, d_dst, dm + 2, dm + 3, dm + 4, d_status, 1,
-                                                      C, c->d_ws, c->d_ws_cap, c->s)
-                        : rle_decode_batch_device_sized(d_src, dm + 0, dm + 1, d_dst, dm + 2, dm + 3, dm + 4, d_status, 1,
-                                                        C, U, c->s);
-    if (drc != RLE_OK) die("decode launch", hipGetLastError());
+    const bool seg = rle::decode_form(C).seg;
+    if (seg) grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, C));
+    launch_decode(c, seg, d_src, d_dst, dm, C, U);
     check(hipMemcpyAsync(hm + 5, dm + 5, sizeof(uint64_t), hipMemcpyDeviceToHost, c->s), "D2H(meta)");
 }
 
@@ -860,6 +843,15 @@ void warn_overflow(const char* who) {
     if (!g_warned_overflow.exchange(1))
         fprintf(stderr, "librle_mi355x: %s: stream decodes past U+E (the reference would overflow its heap block); "
                         "output truncated\n", who);
+}
+
+// The end of an RLEdecompress (its U decoded bytes in the caller's block r already): the E region is
+// zeros, unless a non-encoder stream (st) wrote into it; fetch_tail(dst) copies those E bytes from the slot.
+template <class FetchTail>
+void finish_decode_tail(uint32_t st, char* r, size_t U, size_t E, FetchTail&& fetch_tail) {
+    if (E && (st & RLE_STATUS_SERIAL)) fetch_tail(r + U);
+    else if (E) memset(r + U, 0, E);
+    if (st & RLE_STATUS_OVERFLOW) warn_overflow("RLEdecompress");
 }
 
 // Chunk size of the pipelined transfers: at least 256 KiB, at most kPipeEvents chunks.
@@ -930,24 +922,26 @@ void from_device(Ctx* c, void* dst, const uint8_t* d_src, size_t n) {
     }
 }
 
-// Small calls (one-wave kernels, output <= kOneTripBytes).  Zero-copy (default): the caller's bytes,
+// Small calls (the route's small bodies, rle_route.h).  Zero-copy (default): the caller's bytes,
 // the launch words and the result live in the thread's mapped pinned buffer (kZc* layout).  Copying
 // (RLE_MI355X_SMALL=copy): the launch words travel inside the data copies -- the input words after
 // the caller's bytes in the one H2D, the output length / status after the output slot in the one
 // D2H -- so a call is one H2D, one launch, one D2H, one sync.
 constexpr size_t kMetaBytes = 64;
 
-uint8_t* zc(Ctx* c) {
-    if (!c->h_zc) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&c->h_zc), kZcBytes, hipHostMallocMapped) != hipSuccess) {
+// A mapped pinned buffer of n bytes, made on first use, and its device address.  Throws std::bad_alloc.
+uint8_t* mapped(uint8_t*& h, uint8_t*& d, size_t n) {
+    if (!h) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&h), n, hipHostMallocMapped) != hipSuccess) {
             (void)hipGetLastError();
-            c->h_zc = nullptr;
+            h = nullptr;
             throw std::bad_alloc();
         }
-        check(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_zc), c->h_zc, 0), "hipHostGetDevicePointer");
+        check(hipHostGetDevicePointer(reinterpret_cast<void**>(&d), h, 0), "hipHostGetDevicePointer");
     }
-    return c->h_zc;
+    return h;
 }
+uint8_t* zc(Ctx* c) { return mapped(c->h_zc, c->d_zc, rle::kZcBytes); }
 
 // A new thread context gets its buffers at once: the zero-copy buffer and g_presize bytes of pinned
 // staging and device buffers each way, so that the first medium-size calls do not pay pinned-memory
@@ -958,10 +952,7 @@ void presize(Ctx* c) {
     if (!g_presize) return;
     try {
         zc(c);
-        grow_host(c->h_in, c->h_in_cap, g_presize);
-        grow_host(c->h_out, c->h_out_cap, g_presize);
-        grow_dev(c->d_in, c->d_in_cap, g_presize);
-        grow_dev(c->d_out, c->d_out_cap, g_presize);
+        grow_staging(c, g_presize, g_presize);
     } catch (const std::bad_alloc&) {
     }
 }
@@ -1005,14 +996,7 @@ Combiner g_comb[kMaxDev];
 // in_len, out_off, out_len, out_cap) and the u32 statuses.
 constexpr size_t kCwBytes = 2 * (5 + 1) * 8 * kMaxCoalesce;
 uint64_t* cw(Ctx* c, uint64_t** dev) {
-    if (!c->h_cw) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&c->h_cw), kCwBytes, hipHostMallocMapped) != hipSuccess) {
-            (void)hipGetLastError();
-            c->h_cw = nullptr;
-            throw std::bad_alloc();
-        }
-        check(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_cw), c->h_cw, 0), "hipHostGetDevicePointer");
-    }
+    mapped(c->h_cw, c->d_cw, kCwBytes);
     *dev = reinterpret_cast<uint64_t*>(c->d_cw);
     return reinterpret_cast<uint64_t*>(c->h_cw);
 }
@@ -1102,6 +1086,16 @@ void submit(Ctx* c, Req* r) {
     if (r->result == ~0ull) throw std::bad_alloc();
 }
 
+// One call on c's mapped buffer through the combiner: returns C (encode) or the status (decode).
+uint64_t coalesced(Ctx* c, bool dec, uint64_t in_len, uint64_t out_len, uint64_t cap) {
+    Req r;
+    r.d_buf = c->d_zc; r.in_len = in_len; r.out_len = out_len; r.cap = cap; r.dec = dec; r.result = 0;
+    submit(c, &r);
+    return r.result;
+}
+#else
+// (the product library never sets Settings::coalesce, so no route is Body::MappedCoalesce)
+inline uint64_t coalesced(Ctx*, bool, uint64_t, uint64_t, uint64_t) { die("coalescing: not built in", hipErrorUnknown); }
 #endif  // RLE_VARIANTS
 
 // Launch flags and completion wait of a zero-copy call (g_poll): the status word in the mapped
@@ -1149,13 +1143,14 @@ uint32_t zc_wait(Ctx* c, const uint64_t* status_word) {
 // Measured slower than the per-call launches at 8 threads and behind the server (DESIGN.md §6,
 // profiles/r4r_callrate.txt, r4r_e2e_compare.json), so since round 5 it is built only into the
 // RLE_VARIANTS test library (RLE_MI355X_SERVICE=1 there); the product library carries stubs.
+constexpr uint32_t kSvcStopped = 0xFFFFFFFFu;   // svc_call: not served (below)
 #if RLE_VARIANTS
 // (rle_service.h): one resident workgroup per thread context, on the context's own service stream,
 // its mailbox in the context's mapped buffer.  g_svc_m guards the registry of contexts with a
 // service, which process exit stops (svc_stop).
 extern "C" int rle_service_launch(void* d_mail, const void* d_src, void* d_dst, uint32_t gen, uint32_t done,
                                   void* stream);
-constexpr size_t kZcMail = kZcWords + 2048;   // the mailbox's offset in the mapped buffer (64-byte aligned)
+constexpr size_t kZcMail = rle::kZcWords + 2048;   // the mailbox's offset in the mapped buffer (64-byte aligned)
 constexpr int kSvcMax = 256;                  // contexts with a service at once (the rest launch per call)
 pthread_mutex_t g_svc_m = PTHREAD_MUTEX_INITIALIZER;
 Ctx* g_svc_ctx[kSvcMax];
@@ -1165,7 +1160,7 @@ int g_svc_n = 0;
 bool svc_on(Ctx* c) {
     if (c->svc != -2) return c->svc > 0;
     c->svc = -1;
-    if (!g_service) return false;
+    if (!g_set.service) return false;
     zc(c);
     pthread_mutex_lock(&g_svc_m);
     const bool room = g_svc_n < kSvcMax;
@@ -1197,8 +1192,8 @@ bool svc_ensure(Ctx* c) {
     if (g_svc_stopped.load(std::memory_order_acquire)) return false;
     if (c->svc_gen) check(hipStreamSynchronize(c->svc_s), "hipStreamSynchronize(service)");
     const uint32_t done = __atomic_load_n(&c->svc_h->a.ack, __ATOMIC_ACQUIRE);
-    if (rle_service_launch(c->svc_d, c->d_zc + kZcIn, c->d_zc + kZcOut, c->svc_gen + 1u, done, c->svc_s) != RLE_OK)
-        die("service launch", hipGetLastError());
+    launched(rle_service_launch(c->svc_d, c->d_zc + kZcIn, c->d_zc + kZcOut, c->svc_gen + 1u, done, c->svc_s),
+             "service launch");
     ++c->svc_gen;
     return true;
 }
@@ -1237,7 +1232,6 @@ void svc_stop() {
 // polls that the service has not ended before taking the request.  Once process exit has stopped
 // the services (svc_stop) a request that finds its service gone is not served: kSvcStopped, and the
 // caller takes the launch path (a relaunch would exit at once on the stop word).
-constexpr uint32_t kSvcStopped = 0xFFFFFFFFu;
 uint32_t svc_call(Ctx* c, uint32_t op, uint64_t in_len, uint64_t out_len, uint64_t cap, uint64_t* res_len) {
     rle::SvcReq* r = &c->svc_h->r;
     r->op = op;
@@ -1267,7 +1261,6 @@ uint32_t svc_call(Ctx* c, uint32_t op, uint64_t in_len, uint64_t out_len, uint64
 }
 
 #else
-constexpr uint32_t kSvcStopped = 0xFFFFFFFFu;
 inline bool svc_on(Ctx*) { return false; }
 inline uint32_t svc_call(Ctx*, uint32_t, uint64_t, uint64_t, uint64_t, uint64_t*) { return kSvcStopped; }
 void svc_end(Ctx*) {}
@@ -1285,170 +1278,165 @@ extern "C" int rle_decode_coop_one(const void* src, void* dst, uint64_t C, uint6
                                    uint32_t* d_status, uint32_t flags, void* stream);
 
 namespace {
-char* compress_small_zc(Ctx* c, const char* data, size_t U, size_t* compressedSize) {
-    uint8_t* h = zc(c);
-    memcpy(h + kZcIn, data, U);
-    size_t C;
-    uint32_t st_svc = 0;
-#if RLE_VARIANTS
-    if (g_coalesce) {
-        Req r;
-        r.d_buf = c->d_zc; r.in_len = U; r.out_len = 0; r.cap = 0; r.dec = false; r.result = 0;
-        submit(c, &r);
-        C = r.result;
-    } else
-#endif
-    if (g_zc_seg && U >= g_zc_seg && !(g_zc_coop && U <= rle::kCoopEncMaxBytes)) {   // segmented kernels
-        uint64_t* hw = reinterpret_cast<uint64_t*>(h + kZcWords);
-        hw[0] = kZcIn; hw[1] = U; hw[2] = 0; hw[3] = 0; hw[4] = 0;
-        uint64_t* dw = reinterpret_cast<uint64_t*>(c->d_zc + kZcWords);
-        grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, U));
-        if (rle_encode_batch_device_seg(c->d_zc, dw + 0, dw + 1, c->d_zc + kZcOut, dw + 2, dw + 3,
-                                        reinterpret_cast<uint32_t*>(dw + 4), 1, U, c->d_ws, c->d_ws_cap, c->s) != RLE_OK)
-            die("encode launch", hipGetLastError());
-        check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-        check_encode_status((uint32_t)hw[4]);
-        C = hw[3];
-    } else if (uint64_t Cs = 0; svc_on(c) && (st_svc = svc_call(c, rle::kSvcEncode, U, 0, 0, &Cs)) != kSvcStopped) {
-        check_encode_status(st_svc);
-        C = Cs;
-    } else {
-        uint64_t* hw = reinterpret_cast<uint64_t*>(h + kZcWords);
-        hw[0] = kZcIn; hw[1] = U; hw[2] = 0; hw[3] = 0; hw[4] = kPending;
-        uint64_t* dw = reinterpret_cast<uint64_t*>(c->d_zc + kZcWords);
-        // the sizes by value where the cooperative kernels take the buffer: its first loads do not
-        // wait for the launch words to come over PCIe
-        const int one = rle_encode_coop_one(c->d_zc + kZcIn, c->d_zc + kZcOut, U, dw + 3,
-                                            reinterpret_cast<uint32_t*>(dw + 4), zc_flags(), c->s);
-        if (one < 0) die("encode launch", hipGetLastError());
-        if (one == 0 &&
-            rle_encode_batch_device_sized_flags(c->d_zc, dw + 0, dw + 1, c->d_zc + kZcOut, dw + 2, dw + 3,
-                                                reinterpret_cast<uint32_t*>(dw + 4), 1, U, zc_flags(), c->s) != RLE_OK)
-            die("encode launch", hipGetLastError());
-        check_encode_status(zc_wait(c, hw + 4));
-        C = hw[3];
+// The launch words of a single-buffer launch, in the thread's mapped buffer at rle::kZcWords (zc(c) has
+// made it; no copy commands for them): a decode record [in_off, in_len, out_off, out_len, out_cap,
+// status] or an encode record [in_off, in_len, out_off, out_len, status] from word `at`, h / d its addresses.
+struct ZcWords {
+    enum : size_t { kEncLen = 3, kEncStatus = 4, kDecStatus = 5 };
+    uint64_t *h, *d;
+    static uint64_t* at_word(uint8_t* zc, size_t at) { return reinterpret_cast<uint64_t*>(zc + rle::kZcWords) + at; }
+    explicit ZcWords(const Ctx* c, size_t at = 0) : h(at_word(c->h_zc, at)), d(at_word(c->d_zc, at)) {}
+    void encode(uint64_t in_off, uint64_t U, uint64_t out_off, uint32_t status) const {
+        h[0] = in_off; h[1] = U; h[2] = out_off; h[3] = 0; h[4] = status;
     }
-    *compressedSize = C;
-    char* r = static_cast<char*>(malloc(C + 16));
-    if (!r) return nullptr;
-    memcpy(r, h + kZcOut, C);
-    memset(r + C, 0, 16);
-    return r;
+    void decode(uint64_t in_off, uint64_t C, uint64_t out_off, uint64_t U, uint64_t cap, uint32_t status) const {
+        h[0] = in_off; h[1] = C; h[2] = out_off; h[3] = U; h[4] = cap; h[5] = status;
+    }
+    uint32_t* d_status(size_t word) const { return reinterpret_cast<uint32_t*>(d + word); }
+    size_t encoded_len() const { return h[kEncLen]; }
+    uint32_t status(size_t word) const { return (uint32_t)h[word]; }   // (after a stream synchronize)
+};
+
+// One polled launch (the caller waits: zc_wait) of an encode / a decode between byte offsets in and
+// out of the mapped buffer, record w: the cooperative workgroup, which takes the sizes by value (its
+// first loads do not wait for the launch words to come over PCIe), else one wave (batched entry point).
+void zc_encode_one(Ctx* c, const ZcWords& w, size_t in, size_t U, size_t out) {
+    w.encode(in, U, out, kPending);
+    uint32_t* d_st = w.d_status(ZcWords::kEncStatus);
+    const int one = rle_encode_coop_one(c->d_zc + in, c->d_zc + out, U, w.d + ZcWords::kEncLen, d_st, zc_flags(), c->s);
+    if (one < 0 || (one == 0 && rle_encode_batch_device_sized_flags(c->d_zc, w.d + 0, w.d + 1, c->d_zc, w.d + 2, w.d + 3,
+                                                                   d_st, 1, U, zc_flags(), c->s) != RLE_OK))
+        die("encode launch", hipGetLastError());
+}
+void zc_decode_one(Ctx* c, const ZcWords& w, size_t in, size_t C, size_t out, size_t U, size_t cap) {
+    w.decode(in, C, out, U, cap, kPending);
+    uint32_t* d_st = w.d_status(ZcWords::kDecStatus);
+    const int one = rle_decode_coop_one(c->d_zc + in, c->d_zc + out, C, U, cap, d_st, zc_flags(), c->s);
+    if (one < 0 || (one == 0 && rle_decode_batch_device_sized_flags(c->d_zc, w.d + 0, w.d + 1, c->d_zc, w.d + 2, w.d + 3,
+                                                                   w.d + 4, d_st, 1, C, U, zc_flags(), c->s) != RLE_OK))
+        die("decode launch", hipGetLastError());
 }
 
-void decompress_small_zc(Ctx* c, const char* data, size_t C, size_t U, size_t E, char* r) {
+// RLEcompress on the mapped buffer, by the route's body (rle_route.h); returns the caller's block.
+char* compress_small_zc(Ctx* c, Body body, const char* data, size_t U, size_t* compressedSize) {
+    uint8_t* h = zc(c);
+    memcpy(h + kZcIn, data, U);
+    const ZcWords w(c);
+    uint64_t C = 0;
+    uint32_t st = RLE_STATUS_OK;
+    switch (body) {
+    case Body::MappedCoalesce:
+        C = coalesced(c, false, U, 0, 0);
+        break;
+    case Body::MappedSeg:
+        w.encode(kZcIn, U, 0, 0);
+        grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, U));
+        launched(rle_encode_batch_device_seg(c->d_zc, w.d + 0, w.d + 1, c->d_zc + kZcOut, w.d + 2, w.d + 3,
+                                             w.d_status(ZcWords::kEncStatus), 1, U, c->d_ws, c->d_ws_cap, c->s),
+                 "encode launch");
+        check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
+        st = w.status(ZcWords::kEncStatus);
+        C = w.encoded_len();
+        break;
+    case Body::MappedService:
+        if (svc_on(c) && (st = svc_call(c, rle::kSvcEncode, U, 0, 0, &C)) != kSvcStopped) break;
+        [[fallthrough]];   // (no service on this thread, or stopped at exit: a launch)
+    default:
+        zc_encode_one(c, w, kZcIn, U, kZcOut);
+        st = zc_wait(c, w.h + ZcWords::kEncStatus);
+        C = w.encoded_len();
+    }
+    check_encode_status(st);
+    return make_block(h + kZcOut, nullptr, 0, 0, C, compressedSize);
+}
+
+// RLEdecompress on the mapped buffer into the caller's block r (U + E bytes).
+void decompress_small_zc(Ctx* c, Body body, const char* data, size_t C, size_t U, size_t E, char* r) {
     const size_t total = U + E;
     uint8_t* h = zc(c);
     memcpy(h + kZcIn, data, C);
+    const ZcWords w(c);
     uint32_t st;
-#if RLE_VARIANTS
-    if (g_coalesce) {
-        Req r;
-        r.d_buf = c->d_zc; r.in_len = C; r.out_len = U; r.cap = total; r.dec = true; r.result = 0;
-        submit(c, &r);
-        st = (uint32_t)r.result;
-    } else
-#endif
-    if (g_zc_seg && C >= g_zc_seg && !(g_zc_coop && C <= rle::kCoopDecMaxIn && U <= rle::kCoopDecUmax)) {   // segmented
-        uint64_t* hw = reinterpret_cast<uint64_t*>(h + kZcWords);
-        hw[0] = kZcIn; hw[1] = C; hw[2] = 0; hw[3] = U; hw[4] = total; hw[5] = 0;
-        uint64_t* dw = reinterpret_cast<uint64_t*>(c->d_zc + kZcWords);
+    switch (body) {
+    case Body::MappedCoalesce:
+        st = (uint32_t)coalesced(c, true, C, U, total);
+        break;
+    case Body::MappedSeg:
+        w.decode(kZcIn, C, 0, U, total, 0);
         grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, C));
-        if (rle_decode_batch_device_seg(c->d_zc, dw + 0, dw + 1, c->d_zc + kZcOut, dw + 2, dw + 3, dw + 4,
-                                        reinterpret_cast<uint32_t*>(dw + 5), 1, C, c->d_ws, c->d_ws_cap, c->s) != RLE_OK)
-            die("decode launch", hipGetLastError());
+        launch_decode(c, true, c->d_zc, c->d_zc + kZcOut, w.d, C, U);
         check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-        st = (uint32_t)hw[5];
-    } else if (svc_on(c) && (st = svc_call(c, rle::kSvcDecode, C, U, total, nullptr)) != kSvcStopped) {
-    } else {
-        uint64_t* hw = reinterpret_cast<uint64_t*>(h + kZcWords);
-        hw[0] = kZcIn; hw[1] = C; hw[2] = 0; hw[3] = U; hw[4] = total; hw[5] = kPending;
-        uint64_t* dw = reinterpret_cast<uint64_t*>(c->d_zc + kZcWords);
-        const int one = rle_decode_coop_one(c->d_zc + kZcIn, c->d_zc + kZcOut, C, U, total,
-                                            reinterpret_cast<uint32_t*>(dw + 5), zc_flags(), c->s);
-        if (one < 0) die("decode launch", hipGetLastError());
-        if (one == 0 &&
-            rle_decode_batch_device_sized_flags(c->d_zc, dw + 0, dw + 1, c->d_zc + kZcOut, dw + 2, dw + 3, dw + 4,
-                                                reinterpret_cast<uint32_t*>(dw + 5), 1, C, U, zc_flags(), c->s) != RLE_OK)
-            die("decode launch", hipGetLastError());
-        st = zc_wait(c, hw + 5);
+        st = w.status(ZcWords::kDecStatus);
+        break;
+    case Body::MappedService:
+        if (svc_on(c) && (st = svc_call(c, rle::kSvcDecode, C, U, total, nullptr)) != kSvcStopped) break;
+        [[fallthrough]];
+    default:
+        zc_decode_one(c, w, kZcIn, C, kZcOut, U, total);
+        st = zc_wait(c, w.h + ZcWords::kDecStatus);
     }
     memcpy(r, h + kZcOut, U);
-    if (E) {
-        if (st & RLE_STATUS_SERIAL) memcpy(r + U, h + kZcOut + U, E);
-        else memset(r + U, 0, E);
-    }
-    if (st & RLE_STATUS_OVERFLOW) warn_overflow("RLEdecompress");
+    finish_decode_tail(st, r, U, E, [&](char* dst) { memcpy(dst, h + kZcOut + U, E); });
 }
 
-// RLEcompress of U <= kOneTripBytes bytes; returns the caller's block.
-char* compress_small(Ctx* c, const char* data, size_t U, size_t* compressedSize) {
-    if (g_zerocopy) return compress_small_zc(c, data, U, compressedSize);
+// RLEcompress by a small body of the route (mapped, else the copying form); returns the caller's block.
+char* compress_small(Ctx* c, Body body, const char* data, size_t U, size_t* compressedSize) {
+    if (body != Body::Staged) return compress_small_zc(c, body, data, U, compressedSize);
     const size_t Ur = round16(U), maxC = rle_max_compressed_size(U), Cr = round16(maxC);
-    grow_host(c->h_in, c->h_in_cap, Ur + kMetaBytes);
-    grow_host(c->h_out, c->h_out_cap, Cr + kMetaBytes);
-    grow_dev(c->d_in, c->d_in_cap, Ur + kMetaBytes);
-    grow_dev(c->d_out, c->d_out_cap, Cr + kMetaBytes);
+    grow_staging(c, Ur + kMetaBytes, Cr + kMetaBytes);
     memcpy(c->h_in, data, U);
     uint64_t* hm = reinterpret_cast<uint64_t*>(c->h_in + Ur);
     hm[0] = 0; hm[1] = U; hm[2] = 0;
     check(hipMemcpyAsync(c->d_in, c->h_in, Ur + kMetaBytes, hipMemcpyHostToDevice, c->s), "H2D");
     uint64_t* dm = reinterpret_cast<uint64_t*>(c->d_in + Ur);
     uint64_t* dmo = reinterpret_cast<uint64_t*>(c->d_out + Cr);   // [C, status]
-    if (rle_encode_batch_device_sized(c->d_in, dm + 0, dm + 1, c->d_out, dm + 2, dmo, reinterpret_cast<uint32_t*>(dmo + 1),
-                                      1, U, c->s) != RLE_OK)
-        die("encode launch", hipGetLastError());
+    launched(rle_encode_batch_device_sized(c->d_in, dm + 0, dm + 1, c->d_out, dm + 2, dmo,
+                                           reinterpret_cast<uint32_t*>(dmo + 1), 1, U, c->s), "encode launch");
     check(hipMemcpyAsync(c->h_out, c->d_out, Cr + kMetaBytes, hipMemcpyDeviceToHost, c->s), "D2H");
     check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
     const size_t C = reinterpret_cast<const uint64_t*>(c->h_out + Cr)[0];
     check_encode_status((uint32_t)reinterpret_cast<const uint64_t*>(c->h_out + Cr)[1]);
-    return make_block(c, nullptr, 0, 0, C, compressedSize);
+    return make_block(c->h_out, nullptr, 0, 0, C, compressedSize);
 }
 
-// RLEdecompress of C, U + E <= kOneTripBytes into the caller's block r (U + E bytes).
-void decompress_small(Ctx* c, const char* data, size_t C, size_t U, size_t E, char* r) {
-    if (g_zerocopy) return decompress_small_zc(c, data, C, U, E, r);
+// RLEdecompress by a small body of the route into the caller's block r (U + E bytes).
+void decompress_small(Ctx* c, Body body, const char* data, size_t C, size_t U, size_t E, char* r) {
+    if (body != Body::Staged) return decompress_small_zc(c, body, data, C, U, E, r);
     const size_t total = U + E, Cr = round16(C), Tr = round16(total);
-    grow_host(c->h_in, c->h_in_cap, Cr + kMetaBytes);
-    grow_host(c->h_out, c->h_out_cap, Tr + kMetaBytes);
-    grow_dev(c->d_in, c->d_in_cap, Cr + kMetaBytes);
-    grow_dev(c->d_out, c->d_out_cap, Tr + kMetaBytes);
+    grow_staging(c, Cr + kMetaBytes, Tr + kMetaBytes);
     memcpy(c->h_in, data, C);
     uint64_t* hm = reinterpret_cast<uint64_t*>(c->h_in + Cr);
     hm[0] = 0; hm[1] = C; hm[2] = 0; hm[3] = U; hm[4] = total;
     check(hipMemcpyAsync(c->d_in, c->h_in, Cr + kMetaBytes, hipMemcpyHostToDevice, c->s), "H2D");
     uint64_t* dm = reinterpret_cast<uint64_t*>(c->d_in + Cr);
     uint32_t* d_status = reinterpret_cast<uint32_t*>(c->d_out + Tr);
-    if (rle_decode_batch_device_sized(c->d_in, dm + 0, dm + 1, c->d_out, dm + 2, dm + 3, dm + 4, d_status, 1, C, U, c->s) !=
-        RLE_OK)
-        die("decode launch", hipGetLastError());
+    launched(rle_decode_batch_device_sized(c->d_in, dm + 0, dm + 1, c->d_out, dm + 2, dm + 3, dm + 4, d_status, 1, C, U,
+                                           c->s), "decode launch");
     check(hipMemcpyAsync(c->h_out, c->d_out, Tr + kMetaBytes, hipMemcpyDeviceToHost, c->s), "D2H");
     check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
     const uint32_t st = reinterpret_cast<const uint32_t*>(c->h_out + Tr)[0];
     memcpy(r, c->h_out, U);
-    // the E region: zeros, unless a non-encoder stream wrote into it (it travelled with the rest)
-    if (E) {
-        if (st & RLE_STATUS_SERIAL) memcpy(r + U, c->h_out + U, E);
-        else memset(r + U, 0, E);
-    }
-    if (st & RLE_STATUS_OVERFLOW) warn_overflow("RLEdecompress");
+    finish_decode_tail(st, r, U, E, [&](char* dst) { memcpy(dst, c->h_out + U, E); });   // (it travelled with the rest)
 }
 
+// One small call each way (phase 1 of the start-up): the zero-copy buffer and the stream's first
+// launches.
+void warm_round_trip(Ctx* c, const char* b, size_t n, char* back) {   // (n: a small call either way)
+    size_t C = 0;
+    char* r = compress_small(c, rle::route_compress(n, g_set).body, b, n, &C);
+    if (!r) throw std::bad_alloc();
+    decompress_small(c, rle::route_decompress(C, n, 0, g_set).body, r, C, n, 0, back);
+    free(r);
+}
+void warm_small(Ctx* c) {
+    uint8_t buf[4096], back[4096];
+    for (size_t i = 0; i < sizeof(buf); ++i) buf[i] = (uint8_t)(((i * 2654435761u) >> 13) & 3u);
+    warm_round_trip(c, reinterpret_cast<const char*>(buf), sizeof(buf), reinterpret_cast<char*>(back));
+}
 // One call of every form on a fresh context (preinit_main), so its first real call pays no first
 // use: the zero-copy small calls (one-wave and cooperative kernels), a segmented encode + decode
 // through the pinned staging, and the runtime's pageable-memory copies of large calls (direct
 // staging), which set up the copy engines and the runtime's own staging buffers on first use.
-// One small call each way (phase 1 of the start-up): the zero-copy buffer and the stream's first
-// launches.
-void warm_small(Ctx* c) {
-    uint8_t buf[4096], back[4096];
-    for (size_t i = 0; i < sizeof(buf); ++i) buf[i] = (uint8_t)(((i * 2654435761u) >> 13) & 3u);
-    size_t C = 0;
-    char* r = compress_small(c, reinterpret_cast<const char*>(buf), sizeof(buf), &C);
-    if (!r) throw std::bad_alloc();
-    decompress_small(c, r, C, sizeof(buf), 0, reinterpret_cast<char*>(back));
-    free(r);
-}
 void warm(Ctx* c) {
     const LargeCall lc(c->s);   // (its own buffers; a registration elsewhere only stages its copies)
     constexpr size_t kBig = kPipeMinBytes + (64u << 10), kMed = 64u << 10, kSmall = 4096;
@@ -1456,19 +1444,13 @@ void warm(Ctx* c) {
     for (size_t i = 0; i < kBig; ++i) buf[i] = (uint8_t)(((i * 2654435761u) >> 13) & 3u);   // short runs
     const char* b = reinterpret_cast<const char*>(buf.data());
     char* out = reinterpret_cast<char*>(back.data());
-    size_t C = 0;
-    for (size_t n : {(size_t)16, kSmall}) {
-        char* r = compress_small(c, b, n, &C);
-        if (!r) throw std::bad_alloc();
-        decompress_small(c, r, C, n, 0, out);
-        free(r);
-    }
+    for (size_t n : {(size_t)16, kSmall}) warm_round_trip(c, b, n, out);
     grow_dev(c->d_in, c->d_in_cap, kBig);
     grow_dev(c->d_mid, c->d_mid_cap, kMed);
     to_device(c, c->d_in, b, kMed);
     const bool one_trip = queue_encode(c, c->d_in, kMed);
     check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-    C = fetch_encoded(c, one_trip, 0);
+    const size_t C = fetch_encoded(c, one_trip, 0);
     queue_decode(c, c->d_out, C, c->d_mid, kMed, kMed);
     from_device(c, out, c->d_mid, kMed);
     if (!live_pages(b, kBig) && !live_pages(out, kBig)) {
@@ -1498,24 +1480,28 @@ void reg_input(Ctx* c, const LargeCall& lc, const char* data, size_t n) {
     if (g_reg_kread && rle_copy_in_launch(c->d_in, lc.d_in, n, c->s) == RLE_OK) return;
     check(hipMemcpyAsync(c->d_in, data, n, hipMemcpyHostToDevice, c->s), "H2D");
 }
-}  // namespace
 
-namespace {
 // RLEappend of a small file (old stream decoded by one wave, c^r ‖ new encoded by one wave, output
-// within kOneTripBytes) in one H2D and one D2H:
+// within one trip: rle::AppendRoute::SmallSplice) in one H2D and one D2H:
 //   d_in  = [old stream | splice head (16) | new bytes | launch words]
 //   d_out = [re-encoded tail | result words: C', encode status, decode status, r, head (2)]
 // Returns false (and leaves nothing but d_mid's decoded old content behind) when the final-token
 // check fails and the caller must re-encode whole; *Ce / *r then are meaningless.
 constexpr size_t kAppendWords = 16;
+// Whether content[0, C - *tok) can be kept: the stream's final token (*tok bytes) is the one the
+// encoder emits for the decoded tail ch^r, and the decode (status st) saw encoder output.
+bool final_token_ok(const char* content, size_t C, uint32_t st, size_t r, uint8_t ch, size_t* tok) {
+    const uint8_t* y = reinterpret_cast<const uint8_t*>(content);
+    *tok = r == 1 ? 1 : 3;
+    bool ok = st == RLE_STATUS_OK && r >= 1 && r <= 9 && C >= *tok && y[C - *tok] == ch;
+    if (ok && *tok == 3) ok = y[C - 2] == ch && y[C - 1] == (uint8_t)('0' + r);
+    return ok;
+}
 bool append_small(Ctx* c, const char* content, size_t C, size_t U, const char* add, size_t A, size_t* Ce,
                   size_t* r) {
     const size_t Cr = round16(C), Ar = round16(A), offW = Cr + 16 + Ar, inBytes = offW + 8 * kAppendWords;
     const size_t Er = round16(rle_max_compressed_size(16 + A)), outBytes = Er + 64;
-    grow_host(c->h_in, c->h_in_cap, inBytes);
-    grow_host(c->h_out, c->h_out_cap, outBytes);
-    grow_dev(c->d_in, c->d_in_cap, inBytes);
-    grow_dev(c->d_out, c->d_out_cap, outBytes);
+    grow_staging(c, inBytes, outBytes);
     grow_dev(c->d_mid, c->d_mid_cap, round16(U + A));
     memcpy(c->h_in, content, C);
     if (A) memcpy(c->h_in + Cr + 16, add, A);
@@ -1526,32 +1512,25 @@ bool append_small(Ctx* c, const char* content, size_t C, size_t U, const char* a
     check(hipMemcpyAsync(c->d_in, c->h_in, inBytes, hipMemcpyHostToDevice, c->s), "H2D");
     uint64_t* dw = reinterpret_cast<uint64_t*>(c->d_in + offW);
     uint64_t* res = reinterpret_cast<uint64_t*>(c->d_out + Er);
-    if (rle_decode_batch_device_sized(c->d_in, dw + 0, dw + 1, c->d_mid, dw + 2, dw + 3, dw + 4,
-                                      reinterpret_cast<uint32_t*>(res + 2), 1, C, U, c->s) != RLE_OK)
-        die("decode launch", hipGetLastError());
-    if (rle_append_prepare_launch(c->d_mid, U, c->d_in + Cr, reinterpret_cast<unsigned long long*>(dw + 8), res + 3,
-                                  c->s) != RLE_OK)
-        die("append launch", hipGetLastError());
-    if (rle_encode_batch_device_sized(c->d_in, dw + 5, dw + 6, c->d_out, dw + 7, res + 0, reinterpret_cast<uint32_t*>(res + 1),
-                                      1, 16 + A, c->s) != RLE_OK)
-        die("encode launch", hipGetLastError());
+    launched(rle_decode_batch_device_sized(c->d_in, dw + 0, dw + 1, c->d_mid, dw + 2, dw + 3, dw + 4,
+                                           reinterpret_cast<uint32_t*>(res + 2), 1, C, U, c->s), "decode launch");
+    launched(rle_append_prepare_launch(c->d_mid, U, c->d_in + Cr, reinterpret_cast<unsigned long long*>(dw + 8), res + 3,
+                                       c->s), "append launch");
+    launched(rle_encode_batch_device_sized(c->d_in, dw + 5, dw + 6, c->d_out, dw + 7, res + 0,
+                                           reinterpret_cast<uint32_t*>(res + 1), 1, 16 + A, c->s), "encode launch");
     check(hipMemcpyAsync(c->h_out, c->d_out, outBytes, hipMemcpyDeviceToHost, c->s), "D2H");
     check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
     const uint64_t* hr = reinterpret_cast<const uint64_t*>(c->h_out + Er);
     const uint32_t st = (uint32_t)hr[2];
     const size_t rr = hr[3];
     check_encode_status((uint32_t)hr[1]);
-    const uint8_t ch = reinterpret_cast<const uint8_t*>(hr + 4)[15];
-    const uint8_t* y = reinterpret_cast<const uint8_t*>(content);
-    const size_t tok = rr == 1 ? 1 : 3;
-    bool ok = st == RLE_STATUS_OK && rr >= 1 && rr <= 9 && C >= tok && y[C - tok] == ch;
-    if (ok && tok == 3) ok = y[C - 2] == ch && y[C - 1] == (uint8_t)('0' + rr);
+    size_t tok;
     *Ce = hr[0];
     *r = rr;
-    return ok;
+    return final_token_ok(content, C, st, rr, reinterpret_cast<const uint8_t*>(hr + 4)[15], &tok);
 }
 
-// RLEappend of a small file, zero-copy (round 6; g_zerocopy): the reference's own composition
+// RLEappend of a small file, zero-copy (round 6; rle::AppendRoute::Mapped): the reference's own composition
 // (src/filesystemApi.c:766-775: decode with the new bytes' room, the new bytes at U, encode of the
 // whole) run on this thread's mapped buffer, two launches and one poll, no copy commands:
 //   mapped input  = the old stream, then (once the decode has read it) the new stream
@@ -1559,43 +1538,20 @@ bool append_small(Ctx* c, const char* content, size_t C, size_t U, const char* a
 // For a small file the splice (append_small) saves nothing: its three extra launches cost more
 // than re-encoding a few KiB (r6x: 4 KiB 35.4 µs through the splice on the mapped buffer against
 // 32.8 staged and 26.7 as two drop-in calls).  Exact for any stream, as the composition is the
-// reference's: the decode stops at U (cap U) and the encode covers U + A.  zc_append_fits: what
-// the cooperative or one-wave kernels take from mapped memory.
-bool zc_append_fits(size_t C, size_t U, size_t A) {
-    if (!g_zerocopy || C == 0) return false;
-    const bool dec = C < kSegDecodeBytes || (g_zc_coop && C <= rle::kCoopDecMaxIn && U <= rle::kCoopDecUmax);
-    const bool enc = U + A < kSegEncodeBytes || (g_zc_coop && U + A <= rle::kCoopEncMaxBytes);
-    return dec && enc && C <= kZcWords && U + A <= kZcMaxOut && rle_max_compressed_size(U + A) <= kZcWords;
-}
+// reference's: the decode stops at U (cap U) and the encode covers U + A.
 char* append_small_zc(Ctx* c, const char* content, size_t C, size_t U, const char* add, size_t A, size_t* Cn) {
     uint8_t* h = zc(c);
     memcpy(h + kZcIn, content, C);
     if (A) memcpy(h + kZcOut + U, add, A);
-    uint64_t* hw = reinterpret_cast<uint64_t*>(h + kZcWords);
-    uint64_t* dw = reinterpret_cast<uint64_t*>(c->d_zc + kZcWords);
-    hw[0] = kZcIn; hw[1] = C; hw[2] = kZcOut; hw[3] = U; hw[4] = U; hw[5] = kPending;           // decode
-    hw[6] = kZcOut; hw[7] = U + A; hw[8] = kZcIn; hw[9] = 0; hw[10] = kPending;                // encode
-    // (the sizes by value where the cooperative kernels take them, as compress_small_zc)
-    const int d1 = rle_decode_coop_one(c->d_zc + kZcIn, c->d_zc + kZcOut, C, U, U,
-                                       reinterpret_cast<uint32_t*>(dw + 5), zc_flags(), c->s);
-    if (d1 < 0 || (d1 == 0 && rle_decode_batch_device_sized_flags(c->d_zc, dw + 0, dw + 1, c->d_zc, dw + 2, dw + 3,
-                                                                   dw + 4, reinterpret_cast<uint32_t*>(dw + 5), 1, C,
-                                                                   U, zc_flags(), c->s) != RLE_OK))
-        die("decode launch", hipGetLastError());
-    const int e1 = rle_encode_coop_one(c->d_zc + kZcOut, c->d_zc + kZcIn, U + A, dw + 9,
-                                       reinterpret_cast<uint32_t*>(dw + 10), zc_flags(), c->s);
-    if (e1 < 0 || (e1 == 0 && rle_encode_batch_device_sized_flags(c->d_zc, dw + 6, dw + 7, c->d_zc, dw + 8, dw + 9,
-                                                                   reinterpret_cast<uint32_t*>(dw + 10), 1, U + A,
-                                                                   zc_flags(), c->s) != RLE_OK))
-        die("encode launch", hipGetLastError());
-    check_encode_status(zc_wait(c, hw + 10));
-    const uint32_t st = __atomic_load_n(reinterpret_cast<const uint32_t*>(hw + 5), __ATOMIC_ACQUIRE);
+    const ZcWords wd(c, 0), we(c, 6);
+    zc_decode_one(c, wd, kZcIn, C, kZcOut, U, U);
+    zc_encode_one(c, we, kZcOut, U + A, kZcIn);
+    check_encode_status(zc_wait(c, we.h + ZcWords::kEncStatus));
+    const uint32_t st = __atomic_load_n(reinterpret_cast<const uint32_t*>(wd.h + ZcWords::kDecStatus), __ATOMIC_ACQUIRE);
     if (st & RLE_STATUS_OVERFLOW) warn_overflow("RLEappend");
-    return make_block_from(h + kZcIn, nullptr, 0, 0, hw[9], Cn);
+    return make_block(h + kZcIn, nullptr, 0, 0, we.encoded_len(), Cn);
 }
-}  // namespace
 
-namespace {
 // RLEcompress past the zero-copy reach without registration: the caller's bytes by the runtime's
 // pageable copy (or the pinned staging: live_pages), the tokens back once their count is known.
 // Inside a LargeCall.
@@ -1610,7 +1566,7 @@ char* compress_large(Ctx* c, const char* data, size_t U, size_t* compressedSize)
     const size_t C = c->h_meta[kMetaEnc + 3];
     char* r;
     if (one_trip) {
-        r = make_block(c, nullptr, 0, 0, C, compressedSize);
+        r = make_block(c->h_out, nullptr, 0, 0, C, compressedSize);
     } else {   // the output travels now that C is known, straight into the caller's block
         *compressedSize = C;
         r = static_cast<char*>(malloc(C + 16));
@@ -1619,23 +1575,8 @@ char* compress_large(Ctx* c, const char* data, size_t U, size_t* compressedSize)
             memset(r + C, 0, 16);
         }
     }
-    const uint64_t t3 = now_ns();
-    g_stats.calls_compress++;
-    g_stats.bytes_in += U;
-    g_stats.bytes_out += C;
-    g_stats.bytes_h2d += U;
-    g_stats.bytes_d2h += one_trip ? rle_max_compressed_size(U) : C;
-    g_stats.ns_stage_in += t1 - t0;
-    g_stats.ns_device += t2 - t1;
-    g_stats.ns_stage_out += t3 - t2;
+    g_stats.compress({U, C, U, one_trip ? rle_max_compressed_size(U) : C, t1 - t0, t2 - t1, now_ns() - t2});
     return r;
-}
-
-// Whether an encode of n bytes takes the registered path (g_reg_min; the cooperative kernel's calls
-// stay zero-copy).
-bool registered_encode(size_t n) {
-    return g_reg_min && !g_fake_devs && n >= g_reg_min && n >= kSegEncodeBytes &&
-           !(g_zc_coop && n <= rle::kCoopEncMaxBytes);
 }
 
 // RLEcompress through registered memory (lc registered the caller's U bytes and the result block r
@@ -1647,38 +1588,30 @@ char* compress_registered(Ctx* c, const LargeCall& lc, const char* data, size_t 
     const uint64_t t0 = now_ns();
     // launch words in the thread's mapped buffer (as the zero-copy calls'): no copy commands for them,
     // so the stream is one DMA and four kernels
-    uint64_t* hw = reinterpret_cast<uint64_t*>(c->h_zc + kZcWords);
-    uint64_t* dw = reinterpret_cast<uint64_t*>(c->d_zc + kZcWords);
-    hw[0] = 0; hw[1] = U; hw[2] = 0; hw[3] = 0; hw[4] = 0;
+    const ZcWords w(c);
+    w.encode(0, U, 0, 0);
     reg_input(c, lc, data, U);
-    if (rle_encode_batch_device_seg(c->d_in, dw + 0, dw + 1, c->d_out, dw + 2, dw + 3, reinterpret_cast<uint32_t*>(dw + 4),
-                                    1, U, c->d_ws, c->d_ws_cap, c->s) != RLE_OK)
-        die("encode launch", hipGetLastError());
-    if (rle_copy_len_launch(lc.d_out, c->d_out, dw + 3, maxC, c->s) != RLE_OK) die("copy launch", hipGetLastError());
+    launched(rle_encode_batch_device_seg(c->d_in, w.d + 0, w.d + 1, c->d_out, w.d + 2, w.d + 3,
+                                         w.d_status(w.kEncStatus), 1, U, c->d_ws, c->d_ws_cap, c->s), "encode launch");
+    launched(rle_copy_len_launch(lc.d_out, c->d_out, w.d + ZcWords::kEncLen, maxC, c->s), "copy launch");
     check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-    const size_t C = hw[3];
-    check_encode_status((uint32_t)hw[4]);
+    const size_t C = w.encoded_len();
+    check_encode_status(w.status(ZcWords::kEncStatus));
     // The block keeps its worst-case size (the reference's own block is calloc(2U),
     // src/rleCompression.c:10): shrinking it in place returns the tail to malloc, whose next
     // worst-case block then comes fresh from the kernel each call (r6l: 1 MiB 521 against 87 µs).
     memset(r + C, 0, 16);
     *compressedSize = C;
     g_stats.calls_registered++;
-    g_stats.calls_compress++;
-    g_stats.bytes_in += U;
-    g_stats.bytes_out += C;
-    g_stats.bytes_h2d += U;
-    g_stats.bytes_d2h += C;
-    g_stats.ns_device += now_ns() - t0;
+    g_stats.compress({U, C, U, C, 0, now_ns() - t0, 0});
     return r;
 }
-}  // namespace
 
-static char* compress_impl(char* data, size_t U, size_t* compressedSize) {
+char* compress_impl(char* data, size_t U, size_t* compressedSize) {
     Ctx* c = ctx();
-    const bool reg = registered_encode(U) && reg_likely();
-    const bool small = U < kSegEncodeBytes || (g_zc_seg && g_zerocopy && U <= kZcMaxIn);
-    if (reg) {   // the registered path's buffers, grown before anything is registered
+    const rle::CallRoute rt = rle::route_compress(U, g_set);
+    const bool large = rt.body == Body::Large;
+    if (rt.reg && reg_likely()) {   // the registered path's buffers, grown before anything is registered
         const size_t maxC = rle_max_compressed_size(U);
         zc(c);
         grow_dev(c->d_in, c->d_in_cap, round16(U));
@@ -1690,22 +1623,19 @@ static char* compress_impl(char* data, size_t U, size_t* compressedSize) {
         if (lc.registered()) return compress_registered(c, lc, data, U, r, maxC, compressedSize);
         free(r);
         g_stats.calls_reg_fallback++;
-        if (!small) return compress_large(c, data, U, compressedSize);
-    } else if (!small) {
+        if (large) return compress_large(c, data, U, compressedSize);
+    } else if (large) {
         const LargeCall lc(c->s);
         return compress_large(c, data, U, compressedSize);
     }
-    // one wave walks it, or (g_zc_seg) the segmented kernels on the mapped buffer: the single-copy path
+    // a small body: the single-copy path
     const uint64_t t0 = now_ns();
-    char* r = compress_small(c, data, U, compressedSize);
-    g_stats.calls_compress++;
-    g_stats.bytes_in += U;
-    g_stats.bytes_out += *compressedSize;
-    g_stats.bytes_h2d += round16(U) + kMetaBytes;
-    g_stats.bytes_d2h += round16(rle_max_compressed_size(U)) + kMetaBytes;
-    g_stats.ns_device += now_ns() - t0;
+    char* r = compress_small(c, rt.body, data, U, compressedSize);
+    g_stats.compress({U, *compressedSize, round16(U) + kMetaBytes, round16(rle_max_compressed_size(U)) + kMetaBytes, 0,
+                      now_ns() - t0, 0});
     return r;
 }
+}  // namespace
 
 // src/rleCompression.c:9-45 — returns a malloc block: C token bytes + >= 2 zero bytes; NULL (errno
 // = ENOMEM) when an allocation fails, as the reference's calloc can (:10).
@@ -1729,77 +1659,27 @@ namespace {
 // RLEdecompress through registered memory (as compress_registered; lc registered the caller's C
 // bytes and the result block r of U + E bytes): the decoded bytes copied from device memory into r,
 // and for a stream the encoder cannot have written, whatever it put into the E region.
-void decompress_registered(Ctx* c, const LargeCall& lc, const char* data, size_t C, size_t U, size_t E, char* r) {
+void decompress_registered(Ctx* c, const LargeCall& lc, bool seg, const char* data, size_t C, size_t U, size_t E,
+                           char* r) {
     const size_t total = U + E;
     const uint64_t t0 = now_ns();
-    uint64_t* hw = reinterpret_cast<uint64_t*>(c->h_zc + kZcWords);   // (launch words: compress_registered)
-    uint64_t* dw = reinterpret_cast<uint64_t*>(c->d_zc + kZcWords);
-    hw[0] = 0; hw[1] = C; hw[2] = 0; hw[3] = U; hw[4] = total; hw[5] = 0;
+    const ZcWords w(c);   // (launch words: compress_registered)
+    w.decode(0, C, 0, U, total, 0);
     reg_input(c, lc, data, C);
-    uint32_t* d_status = reinterpret_cast<uint32_t*>(dw + 5);
-    const int drc = C >= kSegDecodeBytes
-                        ? rle_decode_batch_device_seg(c->d_in, dw + 0, dw + 1, c->d_out, dw + 2, dw + 3, dw + 4, d_status,
-                                                      1, C, c->d_ws, c->d_ws_cap, c->s)
-                        : rle_decode_batch_device_sized(c->d_in, dw + 0, dw + 1, c->d_out, dw + 2, dw + 3, dw + 4,
-                                                        d_status, 1, C, U, c->s);
-    if (drc != RLE_OK) die("decode launch", hipGetLastError());
-    if (rle_copy_len_launch(lc.d_out, c->d_out, dw + 3, U, c->s) != RLE_OK) die("copy launch", hipGetLastError());
+    launch_decode(c, seg, c->d_in, c->d_out, w.d, C, U);
+    launched(rle_copy_len_launch(lc.d_out, c->d_out, w.d + 3, U, c->s), "copy launch");
     check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-    const uint32_t st = (uint32_t)hw[5];
-    if (E && (st & RLE_STATUS_SERIAL)) {   // a stream the encoder cannot have written may have put bytes
-        // into the E region: they travel too (rare; one more round trip, inside r's registration)
-        check(hipMemcpyAsync(r + U, c->d_out + U, E, hipMemcpyDeviceToHost, c->s), "D2H");
+    // (E bytes of a non-encoder stream: rare; one more round trip, inside r's registration)
+    finish_decode_tail(w.status(ZcWords::kDecStatus), r, U, E, [&](char* dst) {
+        check(hipMemcpyAsync(dst, c->d_out + U, E, hipMemcpyDeviceToHost, c->s), "D2H");
         check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-    } else if (E) {
-        memset(r + U, 0, E);
-    }
-    if (st & RLE_STATUS_OVERFLOW) warn_overflow("RLEdecompress");
+    });
     g_stats.calls_registered++;
-    g_stats.calls_decompress++;
-    g_stats.bytes_in += C;
-    g_stats.bytes_out += total;
-    g_stats.bytes_h2d += C;
-    g_stats.bytes_d2h += U;
-    g_stats.ns_device += now_ns() - t0;
+    g_stats.decompress({C, total, C, U, 0, now_ns() - t0, 0});
 }
 
 // RLEdecompress past the zero-copy reach without registration (as compress_large).  Inside a
 // LargeCall.
-void decompress_large(Ctx* c, const char* data, size_t C, size_t U, size_t E, char* r);   // below
-}  // namespace
-
-static void decompress_impl(char* data, size_t C, size_t U, size_t E, char* r) {
-    const size_t total = U + E;
-    Ctx* c = ctx();
-    const bool reg = g_reg_min && !g_fake_devs && (C >= g_reg_min || total >= g_reg_min) &&
-                     !(g_zc_coop && C <= rle::kCoopDecMaxIn && U <= rle::kCoopDecUmax) && reg_likely();
-    const bool small = (C < kSegDecodeBytes && total <= kOneTripBytes) ||
-                       (g_zc_seg && g_zerocopy && C <= kZcMaxIn && total <= kZcMaxOut);
-    if (reg) {   // the registered path's buffers, grown before anything is registered
-        zc(c);
-        grow_dev(c->d_in, c->d_in_cap, round16(C));
-        grow_dev(c->d_out, c->d_out_cap, round16(total));
-        if (C >= kSegDecodeBytes) grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, C));
-        const LargeCall lc(c->s, data, C, r, total);
-        if (lc.registered()) return decompress_registered(c, lc, data, C, U, E, r);
-        g_stats.calls_reg_fallback++;
-        if (!small) return decompress_large(c, data, C, U, E, r);
-    } else if (!small) {
-        const LargeCall lc(c->s);
-        return decompress_large(c, data, C, U, E, r);
-    }
-    // one wave walks it, or (g_zc_seg) the segmented kernels on the mapped buffer: the single-copy path
-    const uint64_t t0 = now_ns();
-    decompress_small(c, data, C, U, E, r);
-    g_stats.calls_decompress++;
-    g_stats.bytes_in += C;
-    g_stats.bytes_out += total;
-    g_stats.bytes_h2d += round16(C) + kMetaBytes;
-    g_stats.bytes_d2h += round16(total) + kMetaBytes;
-    g_stats.ns_device += now_ns() - t0;
-}
-
-namespace {
 void decompress_large(Ctx* c, const char* data, size_t C, size_t U, size_t E, char* r) {
     const size_t total = U + E;
     grow_dev(c->d_in, c->d_in_cap, round16(C));
@@ -1811,26 +1691,37 @@ void decompress_large(Ctx* c, const char* data, size_t C, size_t U, size_t E, ch
     from_device(c, r, c->d_out, U);   // also completes the status copy queued before it
     const uint32_t st = (uint32_t)c->h_meta[kMetaDec + 5];
     const uint64_t t2 = now_ns();
-    if (E) {
-        if (st & RLE_STATUS_SERIAL) {  // a non-encoder stream may have written into the E region
-            grow_host(c->h_out, c->h_out_cap, E);
-            check(hipMemcpyAsync(c->h_out, c->d_out + U, E, hipMemcpyDeviceToHost, c->s), "D2H");
-            check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-            memcpy(r + U, c->h_out, E);
-        } else {
-            memset(r + U, 0, E);
-        }
+    finish_decode_tail(st, r, U, E, [&](char* dst) {
+        grow_host(c->h_out, c->h_out_cap, E);
+        check(hipMemcpyAsync(c->h_out, c->d_out + U, E, hipMemcpyDeviceToHost, c->s), "D2H");
+        check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
+        memcpy(dst, c->h_out, E);
+    });
+    g_stats.decompress({C, total, C, U, t1 - t0, t2 - t1, now_ns() - t2});
+}
+
+void decompress_impl(char* data, size_t C, size_t U, size_t E, char* r) {
+    const size_t total = U + E;
+    Ctx* c = ctx();
+    const rle::CallRoute rt = rle::route_decompress(C, U, E, g_set);
+    const bool large = rt.body == Body::Large;
+    if (rt.reg && reg_likely()) {   // the registered path's buffers, grown before anything is registered
+        zc(c);
+        grow_dev(c->d_in, c->d_in_cap, round16(C));
+        grow_dev(c->d_out, c->d_out_cap, round16(total));
+        if (rt.dev.seg) grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, C));
+        const LargeCall lc(c->s, data, C, r, total);
+        if (lc.registered()) return decompress_registered(c, lc, rt.dev.seg, data, C, U, E, r);
+        g_stats.calls_reg_fallback++;
+        if (large) return decompress_large(c, data, C, U, E, r);
+    } else if (large) {
+        const LargeCall lc(c->s);
+        return decompress_large(c, data, C, U, E, r);
     }
-    if (st & RLE_STATUS_OVERFLOW) warn_overflow("RLEdecompress");
-    const uint64_t t3 = now_ns();
-    g_stats.calls_decompress++;
-    g_stats.bytes_in += C;
-    g_stats.bytes_out += total;
-    g_stats.bytes_h2d += C;
-    g_stats.bytes_d2h += U;
-    g_stats.ns_stage_in += t1 - t0;
-    g_stats.ns_device += t2 - t1;
-    g_stats.ns_stage_out += t3 - t2;
+    // a small body: the single-copy path
+    const uint64_t t0 = now_ns();
+    decompress_small(c, rt.body, data, C, U, E, r);
+    g_stats.decompress({C, total, round16(C) + kMetaBytes, round16(total) + kMetaBytes, 0, now_ns() - t0, 0});
 }
 }  // namespace
 
@@ -1856,44 +1747,39 @@ extern "C" char* RLEdecompress(char* data, size_t compressedSize, size_t uncompr
     }
 }
 
+namespace {
+// The splice's fallback (the old stream is not encoder output, or there is none): decode(old) ‖ new
+// re-encoded whole, as the reference does.  d_mid holds the U decoded bytes and d_add, on the
+// device, the A new ones.  Returns the caller's block, *Cn its size.
+char* reencode_whole(Ctx* c, size_t U, const uint8_t* d_add, size_t A, size_t* Cn) {
+    if (A) check(hipMemcpyAsync(c->d_mid + U, d_add, A, hipMemcpyDeviceToDevice, c->s), "D2D");
+    const bool one_trip = queue_encode(c, c->d_mid, U + A);
+    check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
+    const size_t C = fetch_encoded(c, one_trip, 0);   // (may grow h_out)
+    return make_block(c->h_out, nullptr, 0, 0, C, Cn);
+}
+
 // src/filesystemApi.c:766-775 (decode, append, re-encode) fused into one device
 // round trip whose re-encode covers only c^r ‖ newContent (include/rle_fileops.h).
-static char* append_impl(char* content, size_t C, size_t U, const char* newContent, size_t A,
+char* append_impl(char* content, size_t C, size_t U, const char* newContent, size_t A,
                          size_t* newCompressedSize) {
     Ctx* c = ctx();
-    if (zc_append_fits(C, U, A)) {   // zero-copy (append_small_zc)
+    const rle::AppendRoute rt =
+        rle::route_append(C, U, A, rle_max_compressed_size(U + A), rle_max_compressed_size(16 + A), g_set);
+    if (rt == rle::AppendRoute::Mapped) {
         const uint64_t t0 = now_ns();
         char* out = append_small_zc(c, content, C, U, newContent, A, newCompressedSize);
-        g_stats.calls_append++;
-        g_stats.bytes_in += C + A;
-        g_stats.bytes_out += *newCompressedSize;
-        g_stats.bytes_h2d += C + A;
-        g_stats.bytes_d2h += *newCompressedSize;
-        g_stats.ns_device += now_ns() - t0;
+        g_stats.append({C + A, *newCompressedSize, C + A, *newCompressedSize, 0, now_ns() - t0, 0});
         return out;
     }
-    if (C && C < kSegDecodeBytes && 16 + A < kSegEncodeBytes &&
-        rle_max_compressed_size(16 + A) <= kOneTripBytes) {
+    if (rt == rle::AppendRoute::SmallSplice) {
         const uint64_t t0 = now_ns();
         size_t Ce = 0, r = 0;
-        char* out = nullptr;
-        if (append_small(c, content, C, U, newContent, A, &Ce, &r)) {
-            const size_t skip = 16 - r;
-            out = make_block(c, content, C - (r == 1 ? 1 : 3), skip, Ce, newCompressedSize);
-        } else {   // not encoder output: re-encode decode(old) ‖ new whole, as the reference does
-            if (A) check(hipMemcpyAsync(c->d_mid + U, c->d_in + round16(C) + 16, A, hipMemcpyDeviceToDevice, c->s),
-                         "D2D");
-            const bool one_trip = queue_encode(c, c->d_mid, U + A);
-            check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-            const size_t Cn = fetch_encoded(c, one_trip, 0);
-            out = make_block(c, nullptr, 0, 0, Cn, newCompressedSize);
-        }
-        g_stats.calls_append++;
-        g_stats.bytes_in += C + A;
-        g_stats.bytes_out += *newCompressedSize;
-        g_stats.bytes_h2d += round16(C) + 16 + round16(A) + 8 * kAppendWords;
-        g_stats.bytes_d2h += round16(rle_max_compressed_size(16 + A)) + 64;
-        g_stats.ns_device += now_ns() - t0;
+        char* out = append_small(c, content, C, U, newContent, A, &Ce, &r)
+                        ? make_block(c->h_out, content, C - (r == 1 ? 1 : 3), 16 - r, Ce, newCompressedSize)
+                        : reencode_whole(c, U, c->d_in + round16(C) + 16, A, newCompressedSize);
+        g_stats.append({C + A, *newCompressedSize, round16(C) + 16 + round16(A) + 8 * kAppendWords,
+                        round16(rle_max_compressed_size(16 + A)) + 64, 0, now_ns() - t0, 0});
         return out;
     }
     const LargeCall lc(c->s);
@@ -1913,8 +1799,7 @@ static char* append_impl(char* content, size_t C, size_t U, const char* newConte
         check(hipMemsetAsync(c->d_mid, 0, U, c->s), "hipMemsetAsync");
     } else {
         queue_decode(c, c->d_in, C, c->d_mid, U, U);
-        if (rle_append_prepare_device(c->d_mid, U, c->d_in + offA - 16, c->d_meta + kMetaApp, c->s) != RLE_OK)
-            die("append launch", hipGetLastError());
+        launched(rle_append_prepare_device(c->d_mid, U, c->d_in + offA - 16, c->d_meta + kMetaApp, c->s), "append launch");
         check(hipMemcpyAsync(c->h_meta + kMetaApp, c->d_meta + kMetaApp, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost,
                              c->s), "D2H(meta)");
         one_trip = queue_encode(c, c->d_in + offA - 16, 16 + A);
@@ -1922,40 +1807,25 @@ static char* append_impl(char* content, size_t C, size_t U, const char* newConte
     check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
     size_t r = 0, tok = 0;
     if (!full) {
-        // keep content[0, C - tok) only if the stream's final token is the one the encoder emits
-        // for the decoded tail c^r (and the decode saw encoder output)
-        const uint32_t st = (uint32_t)c->h_meta[kMetaDec + 5];
         r = c->h_meta[kMetaApp + 1];
-        const uint8_t ch = reinterpret_cast<const uint8_t*>(c->h_meta + kMetaApp + 2)[15];
-        const uint8_t* y = reinterpret_cast<const uint8_t*>(content);
-        tok = r == 1 ? 1 : 3;
-        bool ok = st == RLE_STATUS_OK && r >= 1 && r <= 9 && C >= tok && y[C - tok] == ch;
-        if (ok && tok == 3) ok = y[C - 2] == ch && y[C - 1] == (uint8_t)('0' + r);
-        full = !ok;
+        full = !final_token_ok(content, C, (uint32_t)c->h_meta[kMetaDec + 5], r,
+                               reinterpret_cast<const uint8_t*>(c->h_meta + kMetaApp + 2)[15], &tok);
     }
     char* out;
-    size_t Cn;
+    size_t d2h;
     if (full) {
-        if (A) check(hipMemcpyAsync(c->d_mid + U, c->d_in + offA, A, hipMemcpyDeviceToDevice, c->s), "D2D");
-        one_trip = queue_encode(c, c->d_mid, U + A);
-        check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-        Cn = fetch_encoded(c, one_trip, 0);
-        out = make_block(c, nullptr, 0, 0, Cn, newCompressedSize);
+        out = reencode_whole(c, U, c->d_in + offA, A, newCompressedSize);
+        d2h = *newCompressedSize;
     } else {
         const size_t skip = 16 - r;   // the filler's single-byte tokens
-        Cn = fetch_encoded(c, one_trip, skip);
-        out = make_block(c, content, C - tok, skip, Cn, newCompressedSize);
+        const size_t Cn = fetch_encoded(c, one_trip, skip);
+        out = make_block(c->h_out, content, C - tok, skip, Cn, newCompressedSize);
+        d2h = Cn - skip;
     }
-    const uint64_t t2 = now_ns();
-    g_stats.calls_append++;
-    g_stats.bytes_in += C + A;
-    g_stats.bytes_out += *newCompressedSize;
-    g_stats.bytes_h2d += C + A;
-    g_stats.bytes_d2h += full ? Cn : Cn - (16 - r);
-    g_stats.ns_stage_in += t1 - t0;
-    g_stats.ns_device += t2 - t1;
+    g_stats.append({C + A, *newCompressedSize, C + A, d2h, t1 - t0, now_ns() - t1, 0});
     return out;
 }
+}  // namespace
 
 extern "C" char* RLEappend(char* content, size_t contentSize, size_t uncompressedSize, const char* newContent,
                            size_t newContentLen, size_t* newCompressedSize) {
@@ -1978,9 +1848,14 @@ extern "C" char* RLEappend(char* content, size_t contentSize, size_t uncompresse
 }
 
 namespace {
-struct NTotals {
-    size_t cin = 0, uout = 0, h2d = 0, d2h = 0;
-    uint64_t ns_in = 0, ns_dev = 0, ns_out = 0;
+struct NTotals : Stats::Call {   // of one RLEdecompressN call: summed over its chunks (add), then its files
+    void add(size_t up, size_t down, uint64_t ns_in, uint64_t ns_dev, uint64_t ns_out) {
+        h2d += up;
+        d2h += down;
+        ns_stage_in += ns_in;
+        ns_device += ns_dev;
+        ns_stage_out += ns_out;
+    }
 };
 
 // RLEdecompressN of one file too large for the bounded staging: straight from / to caller memory
@@ -2022,29 +1897,26 @@ void decompress_n_alone(Ctx* c, const char* data, size_t C, size_t U, char* out,
         }
     }
     if ((uint32_t)c->h_meta[kMetaDec + 5] & RLE_STATUS_OVERFLOW) warn_overflow("RLEdecompressN");
-    t.ns_in += t1 - t0;
-    t.ns_dev += now_ns() - t1;
-    t.h2d += C;
-    t.d2h += U;
+    t.add(C, U, t1 - t0, now_ns() - t1, 0);
 }
 
 // RLEdecompressN of the files idx[0, m) (each C > 0), staged together: one H2D, one launch per
 // kernel form, one D2H.  Their staged sizes sum to at most g_stage_cap each way.
 void decompress_n_chunk(Ctx* c, size_t* idx, size_t m, char* const* data, const size_t* compressedSize,
                         const size_t* uncompressedSize, char* const* out, NTotals& t) {
-    size_t inTot = 0, outTot = 0, maxC = 0;
+    const auto seg = [&](size_t i) {
+        return rle::route_n_file(compressedSize[i], uncompressedSize[i], g_set) == rle::NFileRoute::StagedSeg;
+    };
+    size_t inTot = 0, outTot = 0;
+    bool anySeg = false;
     for (size_t k = 0; k < m; ++k) {
         inTot += round16(compressedSize[idx[k]]);
         outTot += round16(uncompressedSize[idx[k]]);
-        maxC = std::max(maxC, compressedSize[idx[k]]);
+        anySeg = anySeg || seg(idx[k]);
     }
-    // files from kSegDecodeBytes up go to the segmented form, the rest to the one-wave kernel: the
-    // large ones are packed first so that each launch takes a contiguous part of the metadata
-    const size_t mL = maxC >= kSegDecodeBytes
-                          ? (size_t)(std::stable_partition(idx, idx + m,
-                                                           [&](size_t i) { return compressedSize[i] >= kSegDecodeBytes; }) -
-                                     idx)
-                          : 0;
+    // the files of the segmented form are packed first, the one-wave kernel's after them, so that
+    // each launch takes a contiguous part of the metadata
+    const size_t mL = anySeg ? (size_t)(std::stable_partition(idx, idx + m, seg) - idx) : 0;
     size_t inLarge = 0, maxCs = 0, maxUs = 0;
     for (size_t k = 0; k < mL; ++k) inLarge += round16(compressedSize[idx[k]]);
     for (size_t k = mL; k < m; ++k) {   // the one-wave launch's sizes (the cooperative kernels' hint)
@@ -2055,10 +1927,7 @@ void decompress_n_chunk(Ctx* c, size_t* idx, size_t m, char* const* data, const 
     const size_t metaBytes = 32 * m + 4 * m;
     grow_host(c->h_bm, c->h_bm_cap, metaBytes);
     grow_dev(c->d_bm, c->d_bm_cap, round16(metaBytes));
-    grow_host(c->h_in, c->h_in_cap, inTot);
-    grow_host(c->h_out, c->h_out_cap, outTot);
-    grow_dev(c->d_in, c->d_in_cap, inTot);
-    grow_dev(c->d_out, c->d_out_cap, outTot);
+    grow_staging(c, inTot, outTot);
     if (mL) grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes((uint32_t)mL, inLarge));
     const uint64_t t0 = now_ns();
     uint64_t* hb = reinterpret_cast<uint64_t*>(c->h_bm);
@@ -2091,30 +1960,19 @@ void decompress_n_chunk(Ctx* c, size_t* idx, size_t m, char* const* data, const 
         if (U) memcpy(out[i], c->h_out + hb[2 * m + k], U);
         if (hst[k] & RLE_STATUS_OVERFLOW) warn_overflow("RLEdecompressN");
     }
-    t.ns_in += t1 - t0;
-    t.ns_dev += t2 - t1;
-    t.ns_out += now_ns() - t2;
-    t.h2d += inTot;
-    t.d2h += outTot;
+    t.add(inTot, outTot, t1 - t0, t2 - t1, now_ns() - t2);
 }
 
-// A chunk of small files through this thread's mapped buffer (round 6; g_zerocopy): the streams
-// copied into its input region, one launch over them, the decoded files written into its output
-// region, the per-file status words polled (each stored behind a system-scope release of its file),
-// no copy commands.  Files a one-wave or cooperative decode takes (zc_n_fits), at most kZcNFiles
-// (the metadata fits the words region) and the mapped regions' bytes per chunk.
-// (Files up to 16 KiB: a 64 KiB file's one-wave decode writing over PCIe took 200 µs per chunk of
-// five, r6aa: 64 x 64 KiB zero 2266 µs against 456 staged.)
-constexpr size_t kZcNFiles = 56;   // 36 bytes of launch words each, below kZcWords + 2048 (kZcMail)
-constexpr size_t kZcNMaxU = 16384;
-bool zc_n_fits(size_t C, size_t U) {
-    return g_zerocopy && C < kSegDecodeBytes && U <= kZcNMaxU;
-}
+// A chunk of small files through this thread's mapped buffer (round 6; rle::NFileRoute::Mapped): the
+// streams copied into its input region, one launch over them, the decoded files written into its
+// output region, the per-file status words polled (each stored behind a system-scope release of its
+// file), no copy commands.  At most rle::kZcNFiles files (the metadata fits the words region) and the
+// mapped regions' bytes per chunk.
 void decompress_n_chunk_zc(Ctx* c, const size_t* idx, size_t m, char* const* data, const size_t* compressedSize,
                            const size_t* uncompressedSize, char* const* out, NTotals& t) {
     uint8_t* h = zc(c);
-    uint64_t* hw = reinterpret_cast<uint64_t*>(h + kZcWords);
-    uint64_t* dw = reinterpret_cast<uint64_t*>(c->d_zc + kZcWords);
+    const ZcWords w(c);   // (here m records, as arrays: in_off, in_len, out_off, out_len, then m u32 statuses)
+    uint64_t *hw = w.h, *dw = w.d;
     uint32_t* hst = reinterpret_cast<uint32_t*>(hw + 4 * m);
     const uint64_t t0 = now_ns();
     size_t io = 0, oo = 0, maxC = 0, maxU = 0;
@@ -2129,10 +1987,9 @@ void decompress_n_chunk_zc(Ctx* c, const size_t* idx, size_t m, char* const* dat
         maxU = std::max(maxU, U);
     }
     const uint64_t t1 = now_ns();
-    if (rle_decode_batch_device_sized_flags(c->d_zc, dw, dw + m, c->d_zc, dw + 2 * m, dw + 3 * m, nullptr,
-                                            reinterpret_cast<uint32_t*>(dw + 4 * m), (uint32_t)m, maxC, maxU,
-                                            RLE_LAUNCH_STATUS_FLAG, c->s) != RLE_OK)
-        die("decode launch", hipGetLastError());
+    launched(rle_decode_batch_device_sized_flags(c->d_zc, dw, dw + m, c->d_zc, dw + 2 * m, dw + 3 * m, nullptr,
+                                                 reinterpret_cast<uint32_t*>(dw + 4 * m), (uint32_t)m, maxC, maxU,
+                                                 RLE_LAUNCH_STATUS_FLAG, c->s), "decode launch");
     // every file's status (the launch's last stores are in no particular order); zc_wait's bounds
     // and periodic synchronize, counted once per launch
     const uint32_t polled = c->polled;
@@ -2146,11 +2003,7 @@ void decompress_n_chunk_zc(Ctx* c, const size_t* idx, size_t m, char* const* dat
         if (U) memcpy(out[i], h + hw[2 * m + k], U);
         if (hst[k] & RLE_STATUS_OVERFLOW) warn_overflow("RLEdecompressN");
     }
-    t.ns_in += t1 - t0;
-    t.ns_dev += t2 - t1;
-    t.ns_out += now_ns() - t2;
-    t.h2d += io;
-    t.d2h += oo;
+    t.add(io, oo, t1 - t0, t2 - t1, now_ns() - t2);
 }
 
 int decompress_n_impl(size_t n, char* const* data, const size_t* compressedSize, const size_t* uncompressedSize,
@@ -2172,17 +2025,18 @@ int decompress_n_impl(size_t n, char* const* data, const size_t* compressedSize,
     }
     if (idx.empty()) return 0;
     Ctx* c = ctx();
-    NTotals t;
-    // files in batch order: chunks of consecutive small files through the mapped buffer (zc_n_fits),
+    NTotals t{};
+    // files in batch order: chunks of consecutive small files through the mapped buffer (route_n_file),
     // chunks of consecutive files that fit the staging together, files too large for it alone
     size_t k0 = 0, inTot = 0, outTot = 0;
     bool zcChunk = false;
     for (size_t k = 0; k <= idx.size(); ++k) {
         const bool end = k == idx.size();
         const size_t Ci = end ? 0 : round16(compressedSize[idx[k]]), Ui = end ? 0 : round16(uncompressedSize[idx[k]]);
-        const bool zcFile = !end && zc_n_fits(compressedSize[idx[k]], uncompressedSize[idx[k]]);
+        const bool zcFile = !end && rle::route_n_file(compressedSize[idx[k]], uncompressedSize[idx[k]], g_set) ==
+                                        rle::NFileRoute::Mapped;
         const bool alone = !end && (Ci > g_stage_cap || Ui > g_stage_cap);
-        const bool full = zcChunk ? (inTot + Ci > kZcWords || outTot + Ui > kZcMaxOut || k - k0 >= kZcNFiles)
+        const bool full = zcChunk ? (inTot + Ci > rle::kZcWords || outTot + Ui > rle::kZcMaxOut || k - k0 >= rle::kZcNFiles)
                                   : (inTot + Ci > g_stage_cap || outTot + Ui > g_stage_cap);
         if (end || alone || full || (k > k0 && zcFile != zcChunk)) {
             if (k > k0 && zcChunk)
@@ -2203,17 +2057,10 @@ int decompress_n_impl(size_t n, char* const* data, const size_t* compressedSize,
         outTot += Ui;
     }
     for (size_t i : idx) {
-        t.cin += compressedSize[i];
-        t.uout += uncompressedSize[i];
+        t.in += compressedSize[i];
+        t.out += uncompressedSize[i];
     }
-    g_stats.calls_decompress += idx.size();
-    g_stats.bytes_in += t.cin;
-    g_stats.bytes_out += t.uout;
-    g_stats.bytes_h2d += t.h2d;
-    g_stats.bytes_d2h += t.d2h;
-    g_stats.ns_stage_in += t.ns_in;
-    g_stats.ns_device += t.ns_dev;
-    g_stats.ns_stage_out += t.ns_out;
+    g_stats.decompress(t, idx.size());
     return 0;
 }
 }  // namespace
