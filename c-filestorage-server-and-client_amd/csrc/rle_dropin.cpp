@@ -66,6 +66,7 @@ struct Stats {
     std::atomic<uint64_t> ns_stage_in{0}, ns_device{0}, ns_stage_out{0};
     std::atomic<uint64_t> calls_coalesced{0}, launches_coalesced{0};   // zero-copy calls / their combined launches
     std::atomic<uint64_t> calls_registered{0}, calls_reg_fallback{0};  // registered large calls / staged instead
+    std::atomic<uint64_t> calls_append_spliced{0};   // appends that kept the old stream up to its final token
 
     // One finished call of a kind (RLEdecompressN: n of them): caller bytes in / out, bytes moved each
     // way, wall time per phase (a call without staging phases of its own: all device time).
@@ -1775,9 +1776,10 @@ char* append_impl(char* content, size_t C, size_t U, const char* newContent, siz
     if (rt == rle::AppendRoute::SmallSplice) {
         const uint64_t t0 = now_ns();
         size_t Ce = 0, r = 0;
-        char* out = append_small(c, content, C, U, newContent, A, &Ce, &r)
-                        ? make_block(c->h_out, content, C - (r == 1 ? 1 : 3), 16 - r, Ce, newCompressedSize)
-                        : reencode_whole(c, U, c->d_in + round16(C) + 16, A, newCompressedSize);
+        const bool kept = append_small(c, content, C, U, newContent, A, &Ce, &r);
+        char* out = kept ? make_block(c->h_out, content, C - (r == 1 ? 1 : 3), 16 - r, Ce, newCompressedSize)
+                         : reencode_whole(c, U, c->d_in + round16(C) + 16, A, newCompressedSize);
+        if (kept) g_stats.calls_append_spliced++;
         g_stats.append({C + A, *newCompressedSize, round16(C) + 16 + round16(A) + 8 * kAppendWords,
                         round16(rle_max_compressed_size(16 + A)) + 64, 0, now_ns() - t0, 0});
         return out;
@@ -1820,6 +1822,7 @@ char* append_impl(char* content, size_t C, size_t U, const char* newContent, siz
         const size_t skip = 16 - r;   // the filler's single-byte tokens
         const size_t Cn = fetch_encoded(c, one_trip, skip);
         out = make_block(c->h_out, content, C - tok, skip, Cn, newCompressedSize);
+        g_stats.calls_append_spliced++;
         d2h = Cn - skip;
     }
     g_stats.append({C + A, *newCompressedSize, C + A, d2h, t1 - t0, now_ns() - t1, 0});
@@ -2101,6 +2104,7 @@ extern "C" int rle_mi355x_dropin_stats(rle_dropin_stats_t* out, int reset) {
     out->launches_coalesced = g_stats.launches_coalesced.load();
     out->calls_registered = g_stats.calls_registered.load();
     out->calls_reg_fallback = g_stats.calls_reg_fallback.load();
+    out->calls_append_spliced = g_stats.calls_append_spliced.load();
     if (reset) {
         g_stats.calls_compress = 0; g_stats.calls_decompress = 0; g_stats.calls_append = 0; g_stats.bytes_in = 0; g_stats.bytes_out = 0;
         g_stats.bytes_h2d = 0; g_stats.bytes_d2h = 0; g_stats.ns_stage_in = 0; g_stats.ns_device = 0;
@@ -2109,6 +2113,7 @@ extern "C" int rle_mi355x_dropin_stats(rle_dropin_stats_t* out, int reset) {
         g_stats.launches_coalesced = 0;
         g_stats.calls_registered = 0;
         g_stats.calls_reg_fallback = 0;
+        g_stats.calls_append_spliced = 0;
     }
     return RLE_OK;
 }
@@ -2139,13 +2144,14 @@ struct StatsAtExit {
         fprintf(f,
                 "{\"calls_compress\": %llu, \"calls_decompress\": %llu, \"calls_append\": %llu, \"bytes_in\": %llu, \"bytes_out\": %llu, "
                 "\"bytes_h2d\": %llu, \"bytes_d2h\": %llu, \"ns_stage_in\": %llu, \"ns_device\": %llu, "
-                "\"ns_stage_out\": %llu, \"calls_coalesced\": %llu, \"launches_coalesced\": %llu}\n",
+                "\"ns_stage_out\": %llu, \"calls_coalesced\": %llu, \"launches_coalesced\": %llu, "
+                "\"calls_append_spliced\": %llu}\n",
                 (unsigned long long)s.calls_compress, (unsigned long long)s.calls_decompress,
                 (unsigned long long)s.calls_append,
                 (unsigned long long)s.bytes_in, (unsigned long long)s.bytes_out, (unsigned long long)s.bytes_h2d,
                 (unsigned long long)s.bytes_d2h, (unsigned long long)s.ns_stage_in, (unsigned long long)s.ns_device,
                 (unsigned long long)s.ns_stage_out, (unsigned long long)s.calls_coalesced,
-                (unsigned long long)s.launches_coalesced);
+                (unsigned long long)s.launches_coalesced, (unsigned long long)s.calls_append_spliced);
         fclose(f);
     }
 } g_stats_at_exit;

@@ -41,7 +41,8 @@ class DropinStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("calls_compress", "calls_decompress", "bytes_in", "bytes_out",
                                                "bytes_h2d", "bytes_d2h", "ns_stage_in", "ns_device",
                                                "ns_stage_out", "calls_append", "calls_coalesced",
-                                               "launches_coalesced", "calls_registered", "calls_reg_fallback")]
+                                               "launches_coalesced", "calls_registered", "calls_reg_fallback",
+                                               "calls_append_spliced")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -325,6 +326,15 @@ def gen_synthetic(d_out, off, length, kind=None, index=None, stream=None):
                                         _stream_ptr(stream))
     if rc != RLE_OK:
         raise RLEError(f"rle_gen_synthetic_device failed: {rc}")
+
+
+def append_prepare(d_mid, U, d_head, d_meta, stream=None):
+    """rle_append_prepare_device (include/rle_fileops.h): the final run of d_mid[0, U) and the 16-byte
+    splice head of the incremental append.  d_mid: uint8, readable up to round16(U); d_head: 16 bytes;
+    d_meta: 4 int64 (run start, r, the head again)."""
+    rc = lib().rle_append_prepare_device(_ptr(d_mid), int(U), _ptr(d_head), _ptr(d_meta), _stream_ptr(stream))
+    if rc != RLE_OK:
+        raise RLEError(f"rle_append_prepare_device failed: {rc}")
 
 
 def copy_device(dst, src, nbytes, stream=None):

@@ -124,6 +124,9 @@ typedef struct {
     uint64_t calls_registered;     /* large calls run on the caller's registered memory (RLE_MI355X_REG_MIN) */
     uint64_t calls_reg_fallback;   /* ... and those that took the staging instead (registration refused or
                                       overlapping another call's) */
+    uint64_t calls_append_spliced;   /* RLEappend calls that kept the old stream up to its final token and
+                                        re-encoded only the final run's remainder and the new bytes; the
+                                        other appends re-encoded the whole content */
 } rle_dropin_stats_t;
 int rle_mi355x_dropin_stats(rle_dropin_stats_t* out, int reset);
 

@@ -27,7 +27,7 @@ def _runs(rng, n, alpha, maxrun):
     return np.repeat(vals, reps).tobytes()
 
 
-def test_append_final_run_remainders():
+def final_run_cases():
     # old content ending in a run of every length 1..40 (all remainders r = 1..9, several 9-tokens),
     # appended bytes that continue the run, break it, or are empty
     cases = []
@@ -36,17 +36,38 @@ def test_append_final_run_remainders():
             old = b"xy" + ch * L
             for new in (b"", ch, ch * 8, ch * 9, ch * 20 + b"z", b"z", b"zz" + ch, bytes(range(50))):
                 cases.append((old, new))
-    for old, new in cases:
+    return cases
+
+
+def digit_heavy_cases():
+    # streams whose bytes are digits, where the final token cannot be found by reading backwards
+    rng = np.random.default_rng(11)
+    cases = []
+    for i in range(400):
+        old = _runs(rng, int(rng.integers(1, 60)), b"23456789" if i % 2 else b"99a1", 12)
+        new = _runs(rng, int(rng.integers(0, 30)), b"2399", 12)
+        cases.append((old, new))
+    return cases
+
+
+# hand-made streams the encoder never emits: non-canonical final token, bad digits, a stream
+# that decodes past U or short of it -- all re-encoded whole, as the reference does
+NOT_ENCODER_CASES = [(b"aa2aa2", 4, b"ab"), (b"aa1", 1, b"a"), (b"aaz", 1, b"q"), (b"aa9", 3, b"a"),
+                     (b"abc", 5, b"cc"), (b"a", 3, b"\0"), (b"xx5yy7", 12, b"y"), (b"11", 1, b"1")]
+
+
+def test_append_final_run_remainders():
+    """These streams are a few dozen bytes, which RLEappend takes on the mapped buffer (AppendRoute::Mapped:
+    decode and re-encode of the whole); the same cases through the splice are in test_gpu_append_splice.py."""
+    for old, new in final_run_cases():
         y = O.encode(old)
         assert R.append(y, len(old), new) == ref_append(y, len(old), new), (old, new)
 
 
 def test_append_digit_heavy_streams():
-    # streams whose bytes are digits, where the final token cannot be found by reading backwards
-    rng = np.random.default_rng(11)
-    for i in range(400):
-        old = _runs(rng, int(rng.integers(1, 60)), b"23456789" if i % 2 else b"99a1", 12)
-        new = _runs(rng, int(rng.integers(0, 30)), b"2399", 12)
+    """These streams are a few dozen bytes, which RLEappend takes on the mapped buffer (AppendRoute::Mapped:
+    decode and re-encode of the whole); the same cases through the splice are in test_gpu_append_splice.py."""
+    for old, new in digit_heavy_cases():
         y = O.encode(old)
         assert R.append(y, len(old), new) == O.encode(old + new), (old, new)
 
@@ -90,14 +111,13 @@ def test_append_zero_copy_sizes():
 
 
 def test_append_empty_and_not_encoder_streams():
+    """These streams are a few bytes, which RLEappend takes on the mapped buffer (AppendRoute::Mapped:
+    decode and re-encode of the whole); the same cases through the splice are in test_gpu_append_splice.py."""
     assert R.append(b"", 0, b"") == b""
     assert R.append(b"", 0, b"aaab") == b"aa3b"
     # no stream but U > 0: the reference decodes U zero bytes (src/rleCompression.c:48)
     assert R.append(b"", 5, b"ab") == ref_append(b"", 5, b"ab")
-    # hand-made streams the encoder never emits: non-canonical final token, bad digits, a stream
-    # that decodes past U or short of it -- all re-encoded whole, as the reference does
-    for content, U, new in [(b"aa2aa2", 4, b"ab"), (b"aa1", 1, b"a"), (b"aaz", 1, b"q"), (b"aa9", 3, b"a"),
-                            (b"abc", 5, b"cc"), (b"a", 3, b"\0"), (b"xx5yy7", 12, b"y"), (b"11", 1, b"1")]:
+    for content, U, new in NOT_ENCODER_CASES:
         assert R.append(content, U, new) == ref_append(content, U, new), (content, U, new)
 
 

@@ -92,6 +92,46 @@ APPENDS = [
     ("zerocopy=0", 4096, 4096, 4096, "small_splice"),
     ("zerocopy=0", 4096, 61440, 4096, "small_splice"),
     ("zerocopy=0", 40000, 65536, 0, "large_splice"),
+    # the shapes tests/test_gpu_append_splice.py relies on to reach each splice route (the smallest and
+    # largest C, U and A of each of its batteries).  Behind the 66 000-byte run carrier (C about 22 KB):
+    ("", 22005, 66003, 0, "small_splice"),
+    ("", 22005, 66003, 50, "small_splice"),
+    ("", 22010, 66010, 0, "small_splice"),
+    ("", 22010, 66010, 50, "small_splice"),
+    ("", 22226, 66437, 103, "small_splice"),
+    ("", 22106, 66204, 218, "small_splice"),
+    ("", 23369, 70092, 21, "small_splice"),
+    ("", 26102, 78289, 21, "small_splice"),
+    ("", 22005, 66003, 49135, "small_splice"),
+    ("", 22005, 66003, 49136, "large_splice"),
+    ("", 22007, 66011, 140000, "large_splice"),
+    # behind the literal carrier (C past 64 KiB)
+    ("", 66267, 66003, 0, "large_splice"),
+    ("", 66100, 66010, 0, "large_splice"),
+    ("", 66100, 66010, 50, "large_splice"),
+    ("", 66488, 66437, 103, "large_splice"),
+    ("", 70364, 78289, 21, "large_splice"),
+    ("", 66267, 66003, 49135, "large_splice"),
+    ("", 66269, 66011, 140000, "large_splice"),
+    # a file that is one run
+    ("", 22002, 66000, 0, "small_splice"),
+    ("", 22005, 66008, 3, "small_splice"),
+    ("", 33334, 100000, 0, "large_splice"),
+    ("", 33336, 100008, 3, "large_splice"),
+    # streams that are not encoder output (U short of and past the decoded length, no stream) and the
+    # call that fills the decode buffer before each
+    ("", 23334, 70000, 0, "small_splice"),
+    ("", 22010, 66048, 40, "small_splice"),
+    ("", 22009, 66010, 0, "small_splice"),
+    ("", 66272, 66048, 40, "large_splice"),
+    ("", 66271, 66010, 0, "large_splice"),
+    ("", 0, 70000, 40, "large_splice"),
+    # the tiny streams with the zero-copy form off
+    ("zerocopy=0", 1, 1, 0, "small_splice"),
+    ("zerocopy=0", 1, 1, 133, "small_splice"),
+    ("zerocopy=0", 3, 1, 1, "small_splice"),
+    ("zerocopy=0", 222, 435, 103, "small_splice"),
+    ("zerocopy=0", 102, 202, 218, "small_splice"),
 ]
 
 # (settings, C, U, route)
