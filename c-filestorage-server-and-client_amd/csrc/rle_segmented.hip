@@ -1375,6 +1375,13 @@ extern "C" size_t rle_seg_workspace_bytes(uint32_t n, uint64_t total_in_bytes) {
     return carve(nullptr, n, max_segments(n, total_in_bytes, sb)).bytes;
 }
 
+// host only: the segment length a launch with this total_in_bytes takes (tests name it)
+extern "C" uint32_t rle_seg_segment_bytes(uint64_t total_in_bytes) {
+    int ncu = 0;
+    if (device_cus(&ncu) != RLE_OK) ncu = 256;
+    return seg_bytes(total_in_bytes, ncu);
+}
+
 extern "C" int rle_encode_batch_device_seg(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                            void* d_out, const uint64_t* d_out_off, uint64_t* d_out_len,
                                            uint32_t* d_status, uint32_t n, uint64_t total_in_bytes, void* d_workspace,

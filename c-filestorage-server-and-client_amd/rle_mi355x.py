@@ -19,9 +19,11 @@ LIB_PATH = os.environ.get("RLE_MI355X_LIB", LIB_PATH)
 INCLUDE_DIR = os.path.join(os.path.dirname(HERE), "include")
 
 RLE_OK = 0
+RLE_E_INVAL = -1
 RLE_STATUS_OK = 0
 RLE_STATUS_OVERFLOW = 1
 RLE_STATUS_MISALIGNED = 2
+RLE_STATUS_TOOLARGE = 4
 RLE_STATUS_SERIAL = 0x100
 RLE_STATUS_SHORT = 0x400
 RLE_STATUS_INTERNAL = 0x800
@@ -286,6 +288,14 @@ def seg_workspace(n: int, total_in_bytes: int, device=None):
     import torch
     nb = int(lib().rle_seg_workspace_bytes(n, int(total_in_bytes)))
     return torch.empty(nb + 256, dtype=torch.uint8, device=device if device is not None else "cuda")
+
+
+def seg_segment_bytes(total_in_bytes: int) -> int:
+    """The segment length (bytes, a multiple of 1008) a segmented launch with this total_in_bytes
+    takes on the current device (rle_seg_segment_bytes; host only, 256 CUs without a device)."""
+    f = lib().rle_seg_segment_bytes
+    f.restype, f.argtypes = ctypes.c_uint32, [ctypes.c_uint64]
+    return int(f(int(total_in_bytes)))
 
 
 def _ws_ptr(ws):

@@ -18,8 +18,9 @@
  *  - encode: the output slot of buffer i must hold rle_max_compressed_size(d_in_len[i])
  *    bytes; exactly d_out_len[i] = C bytes are written;
  *  - decode: d_in_len[i] = C (compressed), d_out_len[i] = U (decoded size, as the reference's
- *    uncompressedSize).  d_out_cap[i] (NULL: = U) is the writable slot size, U <= cap; the
- *    first U bytes are always written.  Bytes of a slot past U are written only for streams
+ *    uncompressedSize).  d_out_cap[i] (NULL: = U) is the writable slot size, U <= cap (a slot
+ *    with cap < U is refused like a misaligned one: d_status[i] = RLE_STATUS_MISALIGNED, nothing
+ *    written); the first U bytes are always written.  Bytes of a slot past U are written only for streams
  *    the encoder never emits and only where the reference would write them (its
  *    extraAllocation region).
  */
@@ -133,7 +134,7 @@ int rle_mi355x_dropin_stats(rle_dropin_stats_t* out, int reset);
 /* Runs the cross-lane (DPP) primitive self-test on the current device; 0 = pass. */
 int rle_mi355x_selftest(void);
 
-/* Large buffers: the same batched encode / decode with every buffer cut into segments of 4..64
+/* Large buffers: the same batched encode / decode with every buffer cut into segments of 4..16
  * tiles of 1008 input bytes (about 16 segments per CU over the batch) processed by separate waves
  * (per-segment summaries, a per-buffer scan of the run / token phase crossing segment boundaries,
  * then per-segment writes: four launches).  Same arguments, results and status codes as
@@ -146,6 +147,11 @@ int rle_mi355x_selftest(void);
  * RLEcompress / RLEdecompress use it from 48 KiB (encode input) / 32 KiB (decode input).
  * Replaces src/rleCompression.c:9-62 like the entries above. */
 size_t rle_seg_workspace_bytes(uint32_t n, uint64_t total_in_bytes);
+/* Host only, launches nothing: the segment length in bytes (a whole number of 1008-byte tiles) that
+ * a segmented launch with this total_in_bytes takes on the current device:
+ * clamp(ceil(total_in_bytes / 1008) / (16 * CUs), 4, 16) tiles, 256 CUs assumed when no device is
+ * usable.  The same value sizes rle_seg_workspace_bytes.  Tests use it to name the segment edges. */
+uint32_t rle_seg_segment_bytes(uint64_t total_in_bytes);
 int rle_encode_batch_device_seg(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                 void* d_out, const uint64_t* d_out_off, uint64_t* d_out_len,
                                 uint32_t* d_status, uint32_t n, uint64_t total_in_bytes,

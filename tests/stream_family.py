@@ -37,7 +37,7 @@ BAD_DIGITS = (0x30, 0x31, 0x3A, 0x2F, 0x00, 0x7F, 0x80, 0xB5, 0xFF, 0x61)  # 0 1
 NPROBES = 16
 NKINDS = 4
 TILE = 1008            # owned stream bytes of one decode tile
-SEG = 64512            # segment length of the four-launch segmented kernels
+SEG = 64512            # a common multiple of the four-launch kernels' 4-, 8- and 16-tile segments
 SEG_RES = 7056         # segment length of the resident single-pass kernels
 _FILL = (0x71, 0x72, 0x73)   # q r s: literals no prefix alphabet pairs up and no probe value equals
 _CARRIER = 2 * SEG + 8192
@@ -314,6 +314,14 @@ def seg_positions(S):
     return around(S) + around(2 * S) + around(S + TILE, -2, 1)
 
 
+SEG_TILES_BETWEEN = tuple(range(5, 16))   # segment lengths between the shortest (4 tiles) and the longest (16)
+
+
+def seg_length_positions(m):
+    """The first edge of m-tile segments, and for the two shortest odd lengths the second edge."""
+    return around(m * TILE) + (around(2 * m * TILE) if m in (5, 7) else [])
+
+
 def round_positions(waves):
     out = []
     for k in (1, waves - 1, waves, waves + 1):
@@ -330,6 +338,8 @@ def all_positions():
         ps.update(seg_positions(S))
     for w in (4, 8, 16):
         ps.update(round_positions(w))
+    for m in SEG_TILES_BETWEEN:
+        ps.update(seg_length_positions(m))
     return sorted(ps)
 
 

@@ -1,6 +1,8 @@
 """GPU parity of the SEGMENTED codec (several waves per buffer: rle_*_batch_device_seg, the path the
-drop-in takes for large files) against the oracle, bit-exact.  Segments are 64512 input bytes;
-the cases sit on and around segment edges, carry runs and token phases across them (including
+drop-in takes for large files) against the oracle, bit-exact.  The launcher picks the segment
+length per launch (rle_seg_segment_bytes: 4 tiles of 1008 bytes for these launches of a few MB);
+the cases sit on and around multiples of S = 64512, a common multiple of the 4-, 8- and 16-tile
+segment lengths, so on segment edges (every other length: tests/test_gpu_seg_lengths.py), carry runs and token phases across them (including
 '9' runs, whose decode phases never re-synchronise), mix buffer sizes, and feed invalid streams
 that must fall back to the exact serial decoder.  The algebra itself is pinned on CPU by
 tests/test_seg_model.py."""
@@ -14,20 +16,31 @@ import rle_oracle as O
 from test_gpu_parity import gpu_decode, gpu_encode
 
 pytestmark = pytest.mark.gpu
-# segment length of the path under test: 64512 for the four-launch kernels at these batch sizes;
-# 7056 (7 tiles) for the resident single-pass kernels (RLE_MI355X_SEG_RES=1, which
-# test_resident_single_pass below sets for a second run of this module)
+# S: a multiple of the segment length of the path under test.  64512 is a common multiple of the 4-,
+# 8- and 16-tile segments (4032, 8064, 16128 bytes) the four-launch kernels take at these batch
+# sizes (_parity asserts it of every launch); the resident single-pass kernels
+# (RLE_MI355X_SEG_RES=1, which test_resident_single_pass below sets for a second run of this
+# module) have segments of exactly 7056 bytes (7 tiles)
 RES = os.environ.get("RLE_MI355X_SEG_RES", "0") == "1"
 RES_MODE = os.environ.get("RLE_MI355X_SEG_RES", "0")   # "2": the single pass without the resident segment
 S = 7056 if RES else 64512
 
 
+def _edges_are_segment_edges(total_in_bytes):
+    """The launch of this many input bytes has segments that S is a multiple of (the resident run:
+    segments of S bytes), so the cases placed around k * S sit on segment edges."""
+    sb = R.seg_segment_bytes(total_in_bytes)
+    assert sb == S if RES else S % sb == 0, (total_in_bytes, sb, S)
+
+
 def _parity(xs):
+    _edges_are_segment_edges(sum(len(x) for x in xs))
     ys, st = gpu_encode(xs, seg=True)
     assert (st == 0).all(), st
     for i, x in enumerate(xs):
         ref = O.encode(x)
         assert ys[i] == ref, (i, len(x), len(ys[i]), len(ref))
+    _edges_are_segment_edges(sum(len(y) for y in ys))
     dec, st = gpu_decode(ys, [len(x) for x in xs], seg=True)
     for i, x in enumerate(xs):
         assert dec[i] == x, (i, len(x))

@@ -125,14 +125,18 @@ def test_cooperative(group, always_coop):
 def _seg_tiles(total):
     """The launcher's segment length in tiles: a mirror of rle_segmented.hip seg_bytes (about 16
     segments per CU over the batch, 4..16 tiles; the resident single pass has 7-tile segments),
-    which has no query of its own.  The tests below assert this mirror's value, so that they fail
+    checked against the library's own query (rle_seg_segment_bytes).  The tests below assert this
+    mirror's value, so that they fail
     loudly -- rather than quietly test no segment edge -- if seg_bytes changes or the device has
     so few CUs (a partition of the chip) that these launch sizes give another segment length; such
     a failure asks for other launch sizes here, it is no decoder bug."""
     if RES:
-        return 7
-    ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    return min(16, max(4, (total + F.TILE - 1) // F.TILE // (ncu * 16)))
+        tiles = 7
+    else:
+        ncu = torch.cuda.get_device_properties(0).multi_processor_count
+        tiles = min(16, max(4, (total + F.TILE - 1) // F.TILE // (ncu * 16)))
+    assert R.seg_segment_bytes(total) == tiles * F.TILE, (total, tiles, R.seg_segment_bytes(total))
+    return tiles
 
 
 def _seg_decode_in_launches(cases, limit, want_tiles):

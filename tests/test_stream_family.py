@@ -70,6 +70,8 @@ def _groups():
     g[("seg", "resident")] = F.seg_positions(F.SEG_RES)
     for w in (4, 8, 16):
         g[("round", str(w))] = F.round_positions(w)
+    for m in F.SEG_TILES_BETWEEN:
+        g[("seg", "%02d-tiles" % m)] = F.seg_length_positions(m)
     return g
 
 
