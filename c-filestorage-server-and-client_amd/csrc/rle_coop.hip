@@ -33,7 +33,8 @@
 namespace rle {
 
 static_assert(kCoopMaxWaves * kEncStep * kCoopEncRounds == kCoopEncMaxBytes &&
-              kCoopMaxWaves * kTileStep * kCoopDecRounds == kCoopDecMaxIn, "rle_coop_limits.h");
+              kCoopMaxWaves * kTileStep * kCoopDecRounds == kCoopDecMaxIn && kCoopEncTile == kEncStep &&
+              kCoopDecTile == kTileStep, "rle_coop_limits.h");
 
 __device__ __forceinline__ u32 coop_wave() { return uniform(threadIdx.x / kWave); }
 
@@ -681,32 +682,33 @@ bool coop_admits(uint32_t threads, uint32_t n) {
 }
 }  // namespace
 
+// The instantiated forms (rle_coop_limits.h coop_enc_form / coop_dec_form choose among them); each is
+// compiled batched and by value.  A form the selector returned that is not listed here is not
+// launched (0: the caller takes the one-wave kernels), never replaced by another.
+#define RLE_COOP_ENC_FORMS(X) X(2, 1) X(3, 1) X(4, 1) X(6, 1) X(8, 1) X(12, 1) X(16, 1) X(16, 2) X(16, 4)
+#define RLE_COOP_DEC_FORMS(X)                                                                                \
+    X(2, 4096, 1) X(3, 4096, 1) X(5, 4096, 1) X(8, 4096, 1)                                                  \
+    X(2, 16384, 1) X(3, 16384, 1) X(5, 16384, 1) X(8, 16384, 1) X(12, 16384, 1) X(16, 16384, 1) X(16, 16384, 2) \
+    X(4, 32768, 1) X(8, 32768, 1) X(16, 32768, 1) X(16, 32768, 3) X(16, 32768, 4) X(16, 65536, 5)
+
 // Cooperative launches (include/rle_mi355x.h *_sized): 1 if launched, 0 if the batch does not
 // qualify (the caller then uses the one-wave kernels), < 0 on a launch error.
 extern "C" int rle_encode_coop_launch(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, void* d_out,
                                       const uint64_t* d_out_off, uint64_t* d_out_len, uint32_t* d_status, uint32_t n,
                                       uint64_t max_len, uint32_t flags, void* stream) {
-    if (max_len > rle::kEncStep * rle::kCoopMaxWaves * rle::kCoopEncRounds || max_len <= rle::kEncStep) return 0;
-    const uint32_t tiles = (uint32_t)((max_len + rle::kEncStep - 1) / rle::kEncStep);
+    const rle::CoopEncForm f = rle::coop_enc_form(max_len);
+    if (!f.W) return 0;
     if (g_coop_mode.load(std::memory_order_relaxed) == 0) return 0;
     const hipStream_t s = (hipStream_t)stream;
     const uint32_t wt = coop_store_policy(n) | flags;
     const dim3 g(n);
-#define RLE_ENC_COOP(W, R)                                                                                      \
-    do {                                                                                                        \
-        if (!coop_admits<rle::enc_coop_kernel<W, R>>(64 * W, n)) return 0;                                      \
-        hipLaunchKernelGGL((rle::enc_coop_kernel<W, R>), g, dim3(64 * W), 0, s, (const uint8_t*)d_in, d_in_off, \
-                           d_in_len, (uint8_t*)d_out, d_out_off, d_out_len, d_status, n, wt);                   \
-    } while (0)
-    if (tiles <= 2) RLE_ENC_COOP(2, 1);
-    else if (tiles <= 3) RLE_ENC_COOP(3, 1);
-    else if (tiles <= 4) RLE_ENC_COOP(4, 1);
-    else if (tiles <= 6) RLE_ENC_COOP(6, 1);
-    else if (tiles <= 8) RLE_ENC_COOP(8, 1);
-    else if (tiles <= 12) RLE_ENC_COOP(12, 1);
-    else if (tiles <= 16) RLE_ENC_COOP(16, 1);
-    else if (tiles <= 32) RLE_ENC_COOP(16, 2);
-    else RLE_ENC_COOP(16, 4);
+#define RLE_ENC_COOP(W_, R_)                                                                                      \
+    if (f.W == W_ && f.R == R_) {                                                                                 \
+        if (!coop_admits<rle::enc_coop_kernel<W_, R_>>(64 * W_, n)) return 0;                                     \
+        hipLaunchKernelGGL((rle::enc_coop_kernel<W_, R_>), g, dim3(64 * W_), 0, s, (const uint8_t*)d_in, d_in_off, \
+                           d_in_len, (uint8_t*)d_out, d_out_off, d_out_len, d_status, n, wt);                     \
+    } else
+    RLE_COOP_ENC_FORMS(RLE_ENC_COOP) return 0;
 #undef RLE_ENC_COOP
     return hipGetLastError() == hipSuccess ? 1 : RLE_E_HIP;
 }
@@ -715,52 +717,26 @@ extern "C" int rle_decode_coop_launch(const void* d_in, const uint64_t* d_in_off
                                       const uint64_t* d_out_off, const uint64_t* d_out_len, const uint64_t* d_out_cap,
                                       uint32_t* d_status, uint32_t n, uint64_t max_in_len, uint64_t max_out_len,
                                       uint32_t flags, void* stream) {
-    if (max_in_len > (uint64_t)rle::kTileStep * rle::kCoopMaxWaves * rle::kCoopDecRounds ||
-        max_in_len <= rle::kTileStep || max_out_len > rle::kCoopDecUmax)
-        return 0;
-    const uint32_t tiles = (uint32_t)((max_in_len + rle::kTileStep - 1) / rle::kTileStep);
+    const rle::CoopDecForm f = rle::coop_dec_form(max_in_len, max_out_len);
+    if (!f.W) return 0;
     if (g_coop_mode.load(std::memory_order_relaxed) == 0) return 0;
     const hipStream_t s = (hipStream_t)stream;
     const uint32_t wt = coop_store_policy(n) | flags;
     const dim3 g(n);
-#define RLE_DEC_COOP_R(W, UM, R)                                                                                    \
-    do {                                                                                                            \
-        if (!coop_admits<rle::dec_coop_kernel<W, UM, R>>(64 * W, n)) return 0;                                      \
-        hipLaunchKernelGGL((rle::dec_coop_kernel<W, UM, R>), g, dim3(64 * W), 0, s, (const uint8_t*)d_in, d_in_off, \
-                           d_in_len, (uint8_t*)d_out, d_out_off, d_out_len, d_out_cap, d_status, n, wt);            \
-    } while (0)
-#define RLE_DEC_COOP(W, UM) RLE_DEC_COOP_R(W, UM, 1)
-    if (max_out_len > 32768u) {   // 32-64 KiB: rounds of 16 tiles
-        RLE_DEC_COOP_R(16, 65536, 5);
-    } else if (max_out_len > 16384u) {
-        if (tiles <= 4) RLE_DEC_COOP(4, 32768);
-        else if (tiles <= 8) RLE_DEC_COOP(8, 32768);
-        else if (tiles <= 16) RLE_DEC_COOP(16, 32768);
-        else if (tiles <= 48) RLE_DEC_COOP_R(16, 32768, 3);
-        else RLE_DEC_COOP_R(16, 32768, 4);   // (a worst-case 32 KiB stream: up to 49 tiles)
-    } else if (tiles > 16) {   // (random 16 KiB: 17 tiles)
-        RLE_DEC_COOP_R(16, 16384, 2);
-    } else if (max_out_len <= 4096u) {
-        if (tiles <= 2) RLE_DEC_COOP(2, 4096);
-        else if (tiles <= 3) RLE_DEC_COOP(3, 4096);
-        else if (tiles <= 5) RLE_DEC_COOP(5, 4096);
-        else RLE_DEC_COOP(8, 4096);
-    } else {
-        if (tiles <= 2) RLE_DEC_COOP(2, 16384);
-        else if (tiles <= 3) RLE_DEC_COOP(3, 16384);
-        else if (tiles <= 5) RLE_DEC_COOP(5, 16384);
-        else if (tiles <= 8) RLE_DEC_COOP(8, 16384);
-        else if (tiles <= 12) RLE_DEC_COOP(12, 16384);
-        else RLE_DEC_COOP(16, 16384);
-    }
+#define RLE_DEC_COOP(W_, UM_, R_)                                                                                   \
+    if (f.W == W_ && f.Umax == UM_ && f.R == R_) {                                                                  \
+        if (!coop_admits<rle::dec_coop_kernel<W_, UM_, R_>>(64 * W_, n)) return 0;                                  \
+        hipLaunchKernelGGL((rle::dec_coop_kernel<W_, UM_, R_>), g, dim3(64 * W_), 0, s, (const uint8_t*)d_in,       \
+                           d_in_off, d_in_len, (uint8_t*)d_out, d_out_off, d_out_len, d_out_cap, d_status, n, wt);  \
+    } else
+    RLE_COOP_DEC_FORMS(RLE_DEC_COOP) return 0;
 #undef RLE_DEC_COOP
-#undef RLE_DEC_COOP_R
     return hipGetLastError() == hipSuccess ? 1 : RLE_E_HIP;
 }
 
-// One buffer with its sizes by value (csrc/rle_dropin.cpp's zero-copy calls): the same
-// instantiations as the batched launches above choose for these sizes.  1 launched, 0 the buffer
-// does not qualify (the caller launches the one-wave kernels), < 0 a launch error.
+// One buffer with its sizes by value (csrc/rle_dropin.cpp's zero-copy calls): the instantiations
+// the same selector chooses for these sizes.  1 launched, 0 the buffer does not qualify (the caller
+// launches the one-wave kernels), < 0 a launch error.
 namespace {
 bool coop_one_on() {   // (A/B) RLE_MI355X_COOP_ONE=0: the batched entry points for single calls too
     static const bool on = [] {
@@ -773,72 +749,56 @@ bool coop_one_on() {   // (A/B) RLE_MI355X_COOP_ONE=0: the batched entry points 
 extern "C" int rle_encode_coop_one(const void* src, void* dst, uint64_t U, uint64_t* d_out_len, uint32_t* d_status,
                                    uint32_t flags, void* stream) {
     if (!coop_one_on()) return 0;
-    if (U > rle::kEncStep * rle::kCoopMaxWaves * rle::kCoopEncRounds || U <= rle::kEncStep) return 0;
-    const uint32_t tiles = (uint32_t)((U + rle::kEncStep - 1) / rle::kEncStep);
+    const rle::CoopEncForm f = rle::coop_enc_form(U);
+    if (!f.W) return 0;
     if (g_coop_mode.load(std::memory_order_relaxed) == 0) return 0;
     const hipStream_t s = (hipStream_t)stream;
     const uint32_t wt = coop_store_policy(1u) | flags;
-#define RLE_ENC_ONE(W, R)                                                                                          \
-    do {                                                                                                           \
-        if (!coop_admits<rle::enc_coop_kernel<W, R>>(64 * W, 1u)) return 0;                                       \
-        hipLaunchKernelGGL((rle::enc_coop_one_kernel<W, R>), dim3(1), dim3(64 * W), 0, s, (const uint8_t*)src,     \
+#define RLE_ENC_ONE(W_, R_)                                                                                        \
+    if (f.W == W_ && f.R == R_) {                                                                                  \
+        if (!coop_admits<rle::enc_coop_kernel<W_, R_>>(64 * W_, 1u)) return 0;                                     \
+        hipLaunchKernelGGL((rle::enc_coop_one_kernel<W_, R_>), dim3(1), dim3(64 * W_), 0, s, (const uint8_t*)src,  \
                            (uint8_t*)dst, U, d_out_len, d_status, wt);                                             \
-    } while (0)
-    if (tiles <= 2) RLE_ENC_ONE(2, 1);
-    else if (tiles <= 3) RLE_ENC_ONE(3, 1);
-    else if (tiles <= 4) RLE_ENC_ONE(4, 1);
-    else if (tiles <= 6) RLE_ENC_ONE(6, 1);
-    else if (tiles <= 8) RLE_ENC_ONE(8, 1);
-    else if (tiles <= 12) RLE_ENC_ONE(12, 1);
-    else if (tiles <= 16) RLE_ENC_ONE(16, 1);
-    else if (tiles <= 32) RLE_ENC_ONE(16, 2);
-    else RLE_ENC_ONE(16, 4);
+    } else
+    RLE_COOP_ENC_FORMS(RLE_ENC_ONE) return 0;
 #undef RLE_ENC_ONE
     return hipGetLastError() == hipSuccess ? 1 : RLE_E_HIP;
 }
 extern "C" int rle_decode_coop_one(const void* src, void* dst, uint64_t C, uint64_t U, uint64_t cap, uint32_t* d_status,
                                    uint32_t flags, void* stream) {
     if (!coop_one_on()) return 0;
-    if (C > (uint64_t)rle::kTileStep * rle::kCoopMaxWaves * rle::kCoopDecRounds || C <= rle::kTileStep ||
-        U > rle::kCoopDecUmax)
-        return 0;
-    const uint32_t tiles = (uint32_t)((C + rle::kTileStep - 1) / rle::kTileStep);
+    const rle::CoopDecForm f = rle::coop_dec_form(C, U);
+    if (!f.W) return 0;
     if (g_coop_mode.load(std::memory_order_relaxed) == 0) return 0;
     const hipStream_t s = (hipStream_t)stream;
     const uint32_t wt = coop_store_policy(1u) | flags;
-#define RLE_DEC_ONE_R(W, UM, R)                                                                                   \
-    do {                                                                                                          \
-        if (!coop_admits<rle::dec_coop_kernel<W, UM, R>>(64 * W, 1u)) return 0;                                   \
-        hipLaunchKernelGGL((rle::dec_coop_one_kernel<W, UM, R>), dim3(1), dim3(64 * W), 0, s, (const uint8_t*)src, \
-                           (uint8_t*)dst, C, U, cap, d_status, wt);                                               \
-    } while (0)
-#define RLE_DEC_ONE(W, UM) RLE_DEC_ONE_R(W, UM, 1)
-    if (U > 32768u) {   // 32-64 KiB: rounds of 16 tiles
-        RLE_DEC_ONE_R(16, 65536, 5);
-    } else if (U > 16384u) {
-        if (tiles <= 4) RLE_DEC_ONE(4, 32768);
-        else if (tiles <= 8) RLE_DEC_ONE(8, 32768);
-        else if (tiles <= 16) RLE_DEC_ONE(16, 32768);
-        else if (tiles <= 48) RLE_DEC_ONE_R(16, 32768, 3);
-        else RLE_DEC_ONE_R(16, 32768, 4);
-    } else if (tiles > 16) {
-        RLE_DEC_ONE_R(16, 16384, 2);
-    } else if (U <= 4096u) {
-        if (tiles <= 2) RLE_DEC_ONE(2, 4096);
-        else if (tiles <= 3) RLE_DEC_ONE(3, 4096);
-        else if (tiles <= 5) RLE_DEC_ONE(5, 4096);
-        else RLE_DEC_ONE(8, 4096);
-    } else {
-        if (tiles <= 2) RLE_DEC_ONE(2, 16384);
-        else if (tiles <= 3) RLE_DEC_ONE(3, 16384);
-        else if (tiles <= 5) RLE_DEC_ONE(5, 16384);
-        else if (tiles <= 8) RLE_DEC_ONE(8, 16384);
-        else if (tiles <= 12) RLE_DEC_ONE(12, 16384);
-        else RLE_DEC_ONE(16, 16384);
-    }
+#define RLE_DEC_ONE(W_, UM_, R_)                                                                                     \
+    if (f.W == W_ && f.Umax == UM_ && f.R == R_) {                                                                   \
+        if (!coop_admits<rle::dec_coop_kernel<W_, UM_, R_>>(64 * W_, 1u)) return 0;                                  \
+        hipLaunchKernelGGL((rle::dec_coop_one_kernel<W_, UM_, R_>), dim3(1), dim3(64 * W_), 0, s,                    \
+                           (const uint8_t*)src, (uint8_t*)dst, C, U, cap, d_status, wt);                             \
+    } else
+    RLE_COOP_DEC_FORMS(RLE_DEC_ONE) return 0;
 #undef RLE_DEC_ONE
-#undef RLE_DEC_ONE_R
     return hipGetLastError() == hipSuccess ? 1 : RLE_E_HIP;
+}
+
+// Host only, launches nothing (include/rle_mi355x.h): the form the launchers above select for these
+// sizes, whatever the cooperative mode and the residency admission then decide.
+extern "C" int rle_mi355x_coop_form(int decode, uint64_t max_in_len, uint64_t max_out_len, uint32_t* waves,
+                                    uint32_t* umax, uint32_t* rounds) {
+    uint32_t w, u, r;
+    if (decode) {
+        const rle::CoopDecForm f = rle::coop_dec_form(max_in_len, max_out_len);
+        w = f.W, u = f.Umax, r = f.R;
+    } else {
+        const rle::CoopEncForm f = rle::coop_enc_form(max_in_len);
+        w = f.W, u = 0u, r = f.R;
+    }
+    if (waves) *waves = w;
+    if (umax) *umax = u;
+    if (rounds) *rounds = r;
+    return w != 0u;
 }
 
 #if RLE_VARIANTS

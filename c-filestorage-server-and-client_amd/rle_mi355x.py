@@ -105,6 +105,14 @@ def lib():
     L.rle_append_prepare_device.argtypes = [vp, ctypes.c_uint64, vp, vp, vp]
     L.rle_mi355x_set_coop_mode.restype = ctypes.c_int
     L.rle_mi355x_set_coop_mode.argtypes = [ctypes.c_int]
+    u32p = ctypes.POINTER(u32)
+    L.rle_mi355x_coop_form.restype = ctypes.c_int
+    L.rle_mi355x_coop_form.argtypes = [ctypes.c_int, u64, u64, u32p, u32p, u32p]
+    # the by-value cooperative launches of the drop-in's single calls (csrc/rle_coop.hip; test helpers)
+    L.rle_encode_coop_one.restype = ctypes.c_int
+    L.rle_encode_coop_one.argtypes = [vp, vp, u64, vp, vp, u32, vp]
+    L.rle_decode_coop_one.restype = ctypes.c_int
+    L.rle_decode_coop_one.argtypes = [vp, vp, u64, u64, u64, vp, u32, vp]
     L.rle_decode_release_stream.restype = ctypes.c_int
     L.rle_decode_release_stream.argtypes = [vp]
     L.rle_mi355x_set_dec_round.restype = ctypes.c_int
@@ -370,6 +378,43 @@ def set_coop_mode(mode: int):
     when the launch is resident at once (-1, the default; RLE_MI355X_COOP sets it at load)."""
     if lib().rle_mi355x_set_coop_mode(int(mode)) != RLE_OK:
         raise RLEError(f"bad cooperative mode {mode}")
+
+
+def coop_enc_form(max_len: int):
+    """The cooperative encode form (W, R) the launchers select for this largest input length, or None
+    when it does not qualify (rle_mi355x_coop_form; host only, launches nothing)."""
+    w, u, r = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    ok = lib().rle_mi355x_coop_form(0, int(max_len), 0, ctypes.byref(w), ctypes.byref(u), ctypes.byref(r))
+    return (w.value, r.value) if ok else None
+
+
+def coop_dec_form(max_in_len: int, max_out_len: int):
+    """The cooperative decode form (W, Umax, R) for these largest stream and decoded lengths, or None."""
+    w, u, r = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    ok = lib().rle_mi355x_coop_form(1, int(max_in_len), int(max_out_len), ctypes.byref(w), ctypes.byref(u),
+                                    ctypes.byref(r))
+    return (w.value, u.value, r.value) if ok else None
+
+
+def encode_coop_one(d_src, d_dst, U, d_out_len, d_status, flags=0, stream=None) -> int:
+    """Tests: rle_encode_coop_one, the by-value cooperative encode of one buffer (d_src readable up to
+    round16(U), d_dst of max_compressed_size(U) bytes, both 16-byte aligned; d_out_len one int64,
+    d_status one int32).  Returns 1 launched, 0 the size does not qualify (nothing launched)."""
+    rc = lib().rle_encode_coop_one(_ptr(d_src), _ptr(d_dst), int(U), _ptr(d_out_len), _ptr(d_status), int(flags),
+                                   _stream_ptr(stream))
+    if rc < 0:
+        raise RLEError(f"rle_encode_coop_one failed: {rc}")
+    return rc
+
+
+def decode_coop_one(d_src, d_dst, C, U, cap, d_status, flags=0, stream=None) -> int:
+    """Tests: rle_decode_coop_one, the by-value cooperative decode of one stream (d_src readable up to
+    round16(C), d_dst of cap >= U bytes).  Returns 1 launched, 0 the sizes do not qualify."""
+    rc = lib().rle_decode_coop_one(_ptr(d_src), _ptr(d_dst), int(C), int(U), int(cap), _ptr(d_status), int(flags),
+                                   _stream_ptr(stream))
+    if rc < 0:
+        raise RLEError(f"rle_decode_coop_one failed: {rc}")
+    return rc
 
 
 def set_dec_round(waves: int) -> int:

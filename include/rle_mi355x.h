@@ -74,8 +74,8 @@ int rle_decode_batch_device(const void* d_in, const uint64_t* d_in_off, const ui
 
 /* The same two launches with the batch's largest sizes known on the host (max_in_len >= every
  * d_in_len[i]; decode: max_out_len >= every d_out_len[i]).  Few small buffers (encode:
- * max_in_len <= 8 KiB; decode: max_in_len <= 8064 and max_out_len <= 16 KiB; and no more
- * workgroups than the chip holds at once, from the occupancy API) then run the cooperative
+ * 1 KiB < max_in_len <= 64 KiB; decode: 1008 < max_in_len <= 80640 and max_out_len <= 64 KiB; and
+ * no more workgroups than the chip holds at once, from the occupancy API) then run the cooperative
  * kernels, one workgroup per buffer and one wave per tile, so a buffer's tiles run side by side
  * instead of one after another (a single file, a small readN).  Other batches (or
  * RLE_MI355X_COOP=0) take the kernels above.  Output and status are the same bytes. */
@@ -224,6 +224,16 @@ int rle_dist_finalize(void);
  * qualify, -1 residency-gated default; RLE_MI355X_COOP sets the initial mode).  RLE_E_INVAL
  * otherwise. */
 int rle_mi355x_set_coop_mode(int mode);
+
+/* Host only, launches nothing: which cooperative kernel form the sized entry points (and the
+ * drop-in's single calls) select for these sizes.  decode == 0: max_in_len is the encode's largest
+ * input length (max_out_len ignored, *umax = 0); otherwise the decode's largest stream and decoded
+ * lengths.  Returns 1 and the form -- *rounds rounds of *waves waves, decode: a staging of *umax
+ * output bytes -- or 0 (all three 0) when the sizes do not qualify.  Whether a launch then runs the
+ * form still depends on the cooperative mode and the residency admission.  Null pointers are
+ * skipped.  Tests use it to assert which form a launch ran. */
+int rle_mi355x_coop_form(int decode, uint64_t max_in_len, uint64_t max_out_len, uint32_t* waves,
+                         uint32_t* umax, uint32_t* rounds);
 
 /* Tests / A-B: waves per workgroup of the large-batch decode in rounds (0 off, 4, 8 or 16): batches
  * of more than 4096 buffers through the sized entry points whose max_in_len is at least 8 decode
