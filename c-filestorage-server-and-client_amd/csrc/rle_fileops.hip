@@ -8,9 +8,13 @@
 // of 9 and one final token of r = L - 9 floor((L-1)/9) in 1..9 bytes), so encode(old ‖ new) is
 // encode(old) without its final token, followed by encode(c^r ‖ new), c the last byte of old.
 // Only the final run's remainder r has to be known; the old stream's tokens before it are kept.
+// The second half of the file is the same append on streams that stay in device memory, without
+// decoding them: the tail scan and the append in place (rle_tail_batch_device,
+// rle_append_batch_device).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rle_device.h"
 #include "rle_mi355x.h"
 
 namespace rle {
@@ -88,4 +92,228 @@ extern "C" int rle_append_prepare_device(const void* d_mid, uint64_t U, void* d_
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(d_meta, 0, sizeof(uint64_t), s) != hipSuccess) return RLE_E_HIP;
     return rle_append_prepare_launch(d_mid, U, d_head, reinterpret_cast<unsigned long long*>(d_meta), d_meta + 1, s);
+}
+
+// ================================================================ append to stored streams
+// rle_tail_batch_device / rle_append_batch_device (include/rle_mi355x.h): the append of the write
+// path on streams that stay compressed in device memory.  encode(x ‖ new) is encode(x) up to its
+// final token (offset t, byte c, count r) followed by encode(c^r ‖ new) (tests/test_append_model.py),
+// so an append needs (t, r) and the new bytes only.  The tail scan finds (t, r) with the decoder's
+// forward token-phase parse (C bytes read, nothing written); the append re-emits the final token
+// with the new bytes that extend it and then runs the encode tile walk over the new bytes alone,
+// entering it the way a segment of the segmented encode is entered (csrc/rle_segmented.hip
+// enc_seg_write): run start, previous byte and output offset given, the first and the last
+// 16-byte chunk of its output finished with byte stores.
+namespace rle {
+
+constexpr u32 kFileWaves = 4;
+constexpr u32 kFileBlock = kWave * kFileWaves;
+
+// rle_append_slot_bytes, on both sides: C + rle_max_compressed_size(A + 9) rounded up to 16, or 0
+// past the per-buffer limit.
+__host__ __device__ inline uint64_t append_slot_bytes(uint64_t C, uint64_t A) {
+    if (C > RLE_MAX_BUFFER_BYTES || A > RLE_MAX_BUFFER_BYTES) return 0u;
+    const uint64_t u = A + 9u;
+    const uint64_t s = (C + u + u / 2u + 15u) & ~(uint64_t)15u;
+    return s > RLE_MAX_BUFFER_BYTES ? 0u : s;
+}
+
+// One wave per stream: the decode's tiles (LDS-DMA, dec_prepare, dec_lengths) without its scatter,
+// staging and stores.  Per tile: the count-digit validation (a 3-byte token whose digit is not
+// '2'..'9', or lies past C while its second byte does not, stops the walk), the decoded length of the
+// tokens starting in the tile, and the last token start.  Bytes at or past C read as zero
+// (dec_prepare), and a token starting at C - 1 is one byte long whatever they are (dec_lengths).
+__global__ __launch_bounds__(kFileBlock) void tail_scan_kernel(const uint8_t* __restrict__ in,
+                                                               const uint64_t* __restrict__ off,
+                                                               const uint64_t* __restrict__ len,
+                                                               uint64_t* __restrict__ tail,
+                                                               uint64_t* __restrict__ ulen,
+                                                               uint32_t* __restrict__ status, uint32_t n) {
+    __shared__ __attribute__((aligned(16))) uint8_t slots_all[kFileWaves * 2 * kSlot];
+    __shared__ __attribute__((aligned(16))) DecEntry tbl[256];
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    for (u32 k = threadIdx.x; k < 256u; k += kFileBlock) tbl[k] = kDecTable.e[k];
+    __syncthreads();
+    const u32 b = blockIdx.x * kFileWaves + wid;
+    if (b >= n) return;
+    const uint64_t C64 = len[b], ioff = off[b];
+    const uint8_t* src = in + ioff;
+    u32 bad = ((uintptr_t)src & 15u) ? RLE_STATUS_MISALIGNED : 0u;
+    if (C64 > kMaxBufferBytes) bad |= RLE_STATUS_TOOLARGE;
+    uint64_t w = 0u, U = 0u;
+    if (!bad) {
+        const u32 C = (u32)C64;
+        const u32x4 rsi = make_rsrc(src, (C + 15u) & ~15u);
+        const uint8_t* slots = slots_all + wid * 2 * kSlot;
+        const DecK kc = dec_k();
+        constexpr uint64_t kOwned = (1ull << kOwnLanes) - 1ull;
+        u32 d = 0u, last = 0u;
+        const bool stopped = walk_tiles(rsi, 0u, ntiles_for(C), lane, slots, [&](u32 t, const uint8_t* cs, const Refill& nx) {
+            const u32 pos = t * kTileStep;
+            const u32x4 cur = *reinterpret_cast<const u32x4*>(cs + 16u * lane);
+            nx();   // the slot is free once read
+            const DecPrep pr = dec_prepare(cur, pos, C, C, lane, tbl, kc);
+            const DecLen ln = dec_lengths(pr, d);
+            if (__builtin_amdgcn_ballot_w64(ln.serial_lane) & kOwned) return ~0u;
+            U += readlane(wave_scan_incl(ln.nout, 0u, OpAdd()), kOwnLanes - 1u);
+            // the tile's last token start (S80: 0x80 per start among the owned positions)
+            const u32 sa = __builtin_amdgcn_udot4(ln.S80[1], kc.C2, __builtin_amdgcn_udot4(ln.S80[0], kc.C1, 0u, false), false);
+            const u32 sb = __builtin_amdgcn_udot4(ln.S80[3], kc.C2, __builtin_amdgcn_udot4(ln.S80[2], kc.C1, 0u, false), false);
+            const u32 S16 = ((sa >> 7) | (sb << 1)) & 0xFFFFu;
+            const uint64_t has = __builtin_amdgcn_ballot_w64(S16 != 0u) & kOwned;
+            if (has) {
+                const u32 hl = 63u - (u32)__builtin_clzll(has);
+                last = pos + 16u * hl + 31u - (u32)__builtin_clz(readlane(S16, hl));
+            }
+            d = bfe(readlane(pr.incl, kOwnLanes - 1u), 8u * d, 8);
+            return 0u;
+        });
+        vm_drain();
+        if (stopped) {
+            bad = RLE_STATUS_NOTCANON;
+            U = 0u;
+        } else if (C) {
+            // the parse ends at C exactly: the final token is y[C-1] alone or "v v digit"
+            u32 r = 1u;
+            if (last + 1u != C) r = uniform((u32)src[C - 1u]) - 0x30u;
+            if ((last + 1u != C && last + 3u != C) || r < 1u || r > 9u) {
+                bad = RLE_STATUS_NOTCANON;
+                U = 0u;
+            } else {
+                w = (uint64_t)last | ((uint64_t)r << 32);
+            }
+        }
+    }
+    if (lane == 0) {
+        tail[b] = w;
+        if (ulen) ulen[b] = U;
+        if (status) status[b] = bad;
+    }
+}
+
+// One tile of the append's walk: enc_tile with, on the last tile, the start of the buffer's final
+// run (the last run boundary below U; enc_tile_an's own EncState.rs counts the positions past U as
+// boundaries there).
+__device__ __forceinline__ u32 app_tile(const uint8_t* cslot, const Refill& next, u32 pos, u32 U, u32 lane,
+                                        uint8_t* stage, uint8_t* dst, u32x4 rso, EncState& st, const EncK& kc,
+                                        const u32* elut, u32& final_rs) {
+    const u32x4 cur = *reinterpret_cast<const u32x4*>(cslot + 16u * lane);
+    next();   // the slot is free once read
+    const EncAn an = enc_analyze_bounds<false>(cur, uint2{0u, 0u}, pos, U, U, lane, st.prev_top, kc);
+    if (pos + kTileStep >= U) {
+        const u32 left = an.p0 < U ? U - an.p0 : 0u;
+        const u32 Bv = lane < kOwnLanes ? an.B & lowmask(left < 16u ? left : 16u) : 0u;
+        const u32 lb = Bv ? an.p0 + 31u - (u32)__builtin_clz(Bv) : 0u;
+        const u32 m = readlane(wave_scan_incl(lb, 0u, OpMax()), kWave - 1u);
+        final_rs = m > st.rs ? m : st.rs;
+    }
+    return enc_tile_an<false, true>(an, uint2{0u, 0u}, pos, U, U, lane, stage, dst, rso, st, kc, elut);
+}
+
+// One wave per file.  The walk runs over a virtual buffer: 16 head positions (the final token's c^r
+// at 16 - r .. 15, never read) followed by the new bytes at 16 .., entered at position 16 with the
+// run start 16 - r, the previous byte c and the output offset behind the final token, which the
+// wave first writes again with the count r + e (e: the leading new bytes equal to c, up to 9 - r).
+// An empty stream is a plain encode of the new bytes from position 0.
+__global__ __launch_bounds__(kFileBlock) void append_kernel(uint8_t* streams, const uint64_t* __restrict__ off,
+                                                            uint64_t* len, const uint64_t* __restrict__ cap,
+                                                            uint64_t* ulen, uint64_t* tail,
+                                                            const uint8_t* __restrict__ newb,
+                                                            const uint64_t* __restrict__ new_off,
+                                                            const uint64_t* __restrict__ new_len, uint32_t* status,
+                                                            uint32_t n) {
+    __shared__ __attribute__((aligned(16))) uint8_t slots_all[kFileWaves * 2 * kSlot];
+    __shared__ __attribute__((aligned(16))) uint8_t stage_all[kFileWaves * kEncStage];
+    __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];   // enc_tile_fast's selectors
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    for (u32 k = threadIdx.x; k < kInsWaveWords; k += kFileBlock) elut[k] = kEncInsLut.s[k];
+    __syncthreads();
+    const u32 b = blockIdx.x * kFileWaves + wid;
+    if (b >= n) return;
+    // every word of the file is loaded here, before the walk's hand-counted memory operations
+    const uint64_t C64 = len[b], A64 = new_len[b], cp = cap[b], w = tail[b], soff = off[b], noff = new_off[b];
+    const uint64_t ul = ulen ? ulen[b] : 0u;
+    uint8_t* dst = streams + soff;
+    const uint8_t* nw = newb + noff;
+    const uint64_t need = append_slot_bytes(C64, A64);
+    u32 bad = need ? 0u : RLE_STATUS_TOOLARGE;
+    if ((((uintptr_t)dst | (uintptr_t)nw) & 15u) || (need && cp < need)) bad |= RLE_STATUS_MISALIGNED;
+    const u32 C = (u32)C64, A = (u32)A64;
+    const u32 t = (u32)w, r = (u32)(w >> 32);
+    u32 c = 0u;
+    if (!bad) {
+        // the tail word describes the stream's last bytes (read before the first store)
+        if (w == 0u) {
+            if (C) bad = RLE_STATUS_NOTCANON;
+        } else if ((w >> 36) || r < 1u || r > 9u || C64 != (uint64_t)t + (r == 1u ? 1u : 3u)) {
+            bad = RLE_STATUS_NOTCANON;
+        } else {
+            c = uniform((u32)dst[t]);
+            if (r > 1u && (uniform((u32)dst[t + 1u]) != c || uniform((u32)dst[t + 2u]) != 0x30u + r))
+                bad = RLE_STATUS_NOTCANON;
+        }
+    }
+    if (bad || A == 0u) {   // refused, or nothing to append: the file is left as it is
+        if (lane == 0 && status) status[b] = bad;
+        return;
+    }
+    u32 vs = 0u, outp = 0u, rs = 0u;
+    if (C) {
+        const u32 lim = A < 9u - r ? A : 9u - r;
+        const bool eq = lane < lim && nw[lane] == (uint8_t)c;
+        const u32 e = (u32)__builtin_ctzll(__builtin_amdgcn_ballot_w64(!eq));   // <= lim <= 8
+        const u32 rr = r + e;
+        if (e && lane < 3u) dst[t + lane] = (uint8_t)(lane < 2u ? c : 0x30u + rr);
+        vs = 16u;
+        outp = t + (rr == 1u ? 1u : 3u);
+        rs = 16u - r;
+    }
+    const u32 Uv = vs + A;
+    const u32x4 rsi = make_rsrc(reinterpret_cast<const uint8_t*>((uintptr_t)nw - vs), (Uv + 15u) & ~15u);
+    const u32x4 rso = make_rsrc(dst, (u32)need);
+    uint8_t* stage = stage_all + wid * kEncStage;
+    const uint8_t* slots = slots_all + wid * 2 * kSlot;
+    EncState st{outp, outp & ~15u, c << 24, rs, outp & 15u, false, {}};
+    const EncK kc = enc_k();
+    u32 final_rs = rs;
+    walk_tiles(rsi, vs, ntiles_for(A), lane, slots, [&](u32 k, const uint8_t* cs, const Refill& nx) {
+        return app_tile(cs, nx, vs + k * kTileStep, Uv, lane, stage, dst, rso, st, kc, elut, final_rs);
+    });
+    // the final partial chunk (< 16 bytes, staging chunk 1): byte stores, nothing below the walk's
+    // first output byte and nothing past the new length
+    if (lane >= st.head && lane < st.out_pos - st.flushed) dst[st.flushed + lane] = stage[16u + lane];
+    if (lane == 0) {
+        const u32 rn = (Uv - final_rs - 1u) % 9u + 1u;   // the new final token's count
+        len[b] = st.out_pos;
+        tail[b] = (uint64_t)(st.out_pos - (rn == 1u ? 1u : 3u)) | ((uint64_t)rn << 32);
+        if (ulen) ulen[b] = ul + A;
+        if (status) status[b] = RLE_STATUS_OK;
+    }
+}
+
+}  // namespace rle
+
+extern "C" size_t rle_append_slot_bytes(uint64_t C, uint64_t A) { return (size_t)rle::append_slot_bytes(C, A); }
+
+extern "C" int rle_tail_batch_device(const void* d_in, const uint64_t* d_off, const uint64_t* d_len, uint64_t* d_tail,
+                                     uint64_t* d_ulen, uint32_t* d_status, uint32_t n, void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_in || !d_off || !d_len || !d_tail) return RLE_E_INVAL;
+    hipLaunchKernelGGL(rle::tail_scan_kernel, dim3((n + rle::kFileWaves - 1u) / rle::kFileWaves), dim3(rle::kFileBlock),
+                       0, (hipStream_t)stream, (const uint8_t*)d_in, d_off, d_len, d_tail, d_ulen, d_status, n);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+
+extern "C" int rle_append_batch_device(void* d_streams, const uint64_t* d_off, uint64_t* d_len, const uint64_t* d_cap,
+                                       uint64_t* d_ulen, uint64_t* d_tail, const void* d_new,
+                                       const uint64_t* d_new_off, const uint64_t* d_new_len, uint32_t* d_status,
+                                       uint32_t n, void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_streams || !d_off || !d_len || !d_cap || !d_tail || !d_new || !d_new_off || !d_new_len) return RLE_E_INVAL;
+    hipLaunchKernelGGL(rle::append_kernel, dim3((n + rle::kFileWaves - 1u) / rle::kFileWaves), dim3(rle::kFileBlock), 0,
+                       (hipStream_t)stream, (uint8_t*)d_streams, d_off, d_len, d_cap, d_ulen, d_tail,
+                       (const uint8_t*)d_new, d_new_off, d_new_len, d_status, n);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }

@@ -27,6 +27,9 @@ RLE_STATUS_TOOLARGE = 4
 RLE_STATUS_SERIAL = 0x100
 RLE_STATUS_SHORT = 0x400
 RLE_STATUS_INTERNAL = 0x800
+RLE_STATUS_NOTCANON = 0x1000
+RLE_TAIL_EMPTY = 0
+RLE_MAX_BUFFER_BYTES = 0x7FFFFFF0
 RLE_LAUNCH_STATUS_FLAG = 2
 
 _u64p = ctypes.c_void_p
@@ -103,6 +106,12 @@ def lib():
     L.RLEdecompressN.argtypes = [sz, vp, vp, vp, vp]
     L.rle_append_prepare_device.restype = ctypes.c_int
     L.rle_append_prepare_device.argtypes = [vp, ctypes.c_uint64, vp, vp, vp]
+    L.rle_append_slot_bytes.restype = sz
+    L.rle_append_slot_bytes.argtypes = [u64, u64]
+    L.rle_tail_batch_device.restype = ctypes.c_int
+    L.rle_tail_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp]
+    L.rle_append_batch_device.restype = ctypes.c_int
+    L.rle_append_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
     L.rle_mi355x_set_coop_mode.restype = ctypes.c_int
     L.rle_mi355x_set_coop_mode.argtypes = [ctypes.c_int]
     u32p = ctypes.POINTER(u32)
@@ -353,6 +362,53 @@ def append_prepare(d_mid, U, d_head, d_meta, stream=None):
     rc = lib().rle_append_prepare_device(_ptr(d_mid), int(U), _ptr(d_head), _ptr(d_meta), _stream_ptr(stream))
     if rc != RLE_OK:
         raise RLEError(f"rle_append_prepare_device failed: {rc}")
+
+
+def append_slot_bytes(C: int, A: int) -> int:
+    """rle_append_slot_bytes: the slot capacity an append of A bytes to a C-byte stream may need
+    (C + max_compressed_size(A + 9), rounded up to 16); 0 past RLE_MAX_BUFFER_BYTES.  Host only."""
+    return int(lib().rle_append_slot_bytes(int(C), int(A)))
+
+
+def tail_word(t: int, r: int) -> int:
+    """The tail word of a stream whose final token starts at offset t with count r."""
+    return int(t) | (int(r) << 32)
+
+
+def tail_offset(w: int) -> int:
+    return int(w) & 0xFFFFFFFF
+
+
+def tail_count(w: int) -> int:
+    return (int(w) >> 32) & 0xF
+
+
+def tail_batch(d_in, off, length, tail, ulen=None, status=None, stream=None):
+    """rle_tail_batch_device on device tensors (uint8 streams; int64 offsets, lengths, tail words and
+    decoded lengths; int32 status): the tail word t | r << 32 and the decoded length of every stream,
+    reading the streams only."""
+    rc = lib().rle_tail_batch_device(_ptr(d_in), _ptr(off), _ptr(length), _ptr(tail), _ptr(ulen), _ptr(status),
+                                     off.numel(), _stream_ptr(stream))
+    if rc != RLE_OK:
+        raise RLEError(f"rle_tail_batch_device failed: {rc}")
+
+
+def append_batch(d_streams, off, length, cap, ulen, d_new, new_off, new_len, status=None, tail=None, stream=None):
+    """rle_append_batch_device on device tensors: new_len[i] bytes at d_new + new_off[i] appended to
+    the stream in the slot d_streams + off[i] (length[i] bytes of cap[i]), in place; length, ulen
+    (may be None) and tail are updated.  tail=None: the tail words come from a scan of the streams
+    first (tail_batch) into a fresh tensor.  Returns the tail tensor, to be carried into the next
+    append."""
+    if tail is None:
+        import torch
+        tail = torch.zeros(off.numel(), dtype=torch.int64, device=d_streams.device)
+        tail_batch(d_streams, off, length, tail, None, None, stream)
+    rc = lib().rle_append_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen), _ptr(tail),
+                                       _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(status), off.numel(),
+                                       _stream_ptr(stream))
+    if rc != RLE_OK:
+        raise RLEError(f"rle_append_batch_device failed: {rc}")
+    return tail
 
 
 def copy_device(dst, src, nbytes, stream=None):

@@ -53,6 +53,8 @@ extern "C" {
                                           (not encoder output) */
 #define RLE_STATUS_INTERNAL    0x800u  /* the segmented kernels' carry wait ran out (never expected): output
                                           not trusted */
+#define RLE_STATUS_NOTCANON    0x1000u /* tail scan / append: the stream, or the tail word given for it, is not
+                                          what the encoder emits; nothing written */
 
 /* Worst-case compressed size of U bytes (every run of length 2: 3 bytes per 2 input bytes). */
 size_t rle_max_compressed_size(size_t U);
@@ -171,6 +173,64 @@ int rle_decode_batch_device_seg(const void* d_in, const uint64_t* d_in_off, cons
  * d_meta (4 u64, device): [0] final run start, [1] r, [2..3] a copy of the head.  Asynchronous on
  * `stream`; RLE_E_INVAL when U == 0. */
 int rle_append_prepare_device(const void* d_mid, uint64_t U, void* d_head, uint64_t* d_meta, void* stream);
+
+/* ---- append to stored streams, on the device, without decoding them ---------
+ * The write path of the reference appends by decode, append, re-encode (src/filesystemApi.c:766-775).
+ * For streams kept compressed in device memory the same result needs only the stream's final token
+ * and the new bytes: encode(x ‖ new) = y[0, t) ‖ encode(c^r ‖ new), with y = encode(x), t the
+ * offset of y's final token, c = y[t] and r that token's count.
+ *
+ * The tail word, one uint64_t per stream: bits 0..31 = t, bits 32..35 = r (1 for a one-byte token,
+ * 2..9 for "v v digit"), every other bit zero; RLE_TAIL_EMPTY (0) is the empty stream (C = 0). */
+#define RLE_TAIL_EMPTY      ((uint64_t)0)
+#define RLE_TAIL_OFFSET(w)  ((uint32_t)((uint64_t)(w) & 0xFFFFFFFFu))
+#define RLE_TAIL_COUNT(w)   ((uint32_t)(((uint64_t)(w) >> 32) & 0xFu))
+
+/* Host only, launches nothing: the slot capacity an append of A bytes to a C-byte stream may need,
+ * C + rle_max_compressed_size(A + 9) rounded up to 16 (t < C and r <= 9, so the new length is at most
+ * t + rle_max_compressed_size(r + A)); 0 when that passes RLE_MAX_BUFFER_BYTES. */
+size_t rle_append_slot_bytes(uint64_t C, uint64_t A);
+
+/* Tail scan of n streams (stream i: d_in + d_off[i], d_len[i] = C bytes, 16-byte aligned, readable
+ * up to C rounded up to 16), one wave per stream: the decoder's forward token parse, reading C
+ * bytes and writing only the results.  Bytes at or past C are not part of the stream: a token
+ * starting at C - 1 is one byte whatever lies in the padding.
+ *     j = 0; U = 0
+ *     while j < C:
+ *         if j + 1 < C and y[j] == y[j+1]:
+ *             if j + 2 >= C or not ('2' <= y[j+2] <= '9'): NOTCANON
+ *             t, r = j, y[j+2] - '0'; U += r; j += 3
+ *         else:
+ *             t, r = j, 1;            U += 1; j += 1
+ * RLE_STATUS_OK: d_tail[i] = t | r << 32 and d_ulen[i] = U (64-bit: it may exceed 2 GiB); C = 0 is
+ * OK with tail 0 and ulen 0.  RLE_STATUS_NOTCANON, RLE_STATUS_MISALIGNED (the stream's address) and
+ * RLE_STATUS_TOOLARGE (C > RLE_MAX_BUFFER_BYTES): tail 0 and ulen 0.  d_ulen and d_status may be
+ * NULL.  One wave per stream is the only form: a segmented scan for very large single streams is
+ * not provided. */
+int rle_tail_batch_device(const void* d_in, const uint64_t* d_off, const uint64_t* d_len, uint64_t* d_tail,
+                          uint64_t* d_ulen, uint32_t* d_status, uint32_t n, void* stream);
+
+/* Append in place, one wave per file: file i's stream is d_streams + d_off[i], d_len[i] = C bytes in
+ * a slot of d_cap[i] bytes; its new content is d_new + d_new_off[i], d_new_len[i] = A bytes (readable
+ * up to A rounded up to 16; bytes past A are ignored); d_tail[i] = the stream's tail word (from
+ * rle_tail_batch_device, or carried from the previous append).  d_ulen and d_status may be NULL.
+ * Accepted when the tail word is RLE_TAIL_EMPTY with C = 0, or describes the stream's last bytes
+ * (r = 1: t + 1 = C; else t + 3 = C, y[t] = y[t+1] and y[t+2] = '0' + r).  Then the slot becomes
+ * y[0, t) ‖ encode(c^r ‖ new) (an empty stream: encode(new)): no byte below t and no byte at or past
+ * the new length C' changes; d_len[i] = C', d_ulen[i] += A, d_tail[i] = the new stream's tail word.
+ * A = 0 is OK and changes nothing.
+ * Refused, with the slot, d_len, d_ulen and d_tail untouched:
+ *   RLE_STATUS_NOTCANON    the tail word does not describe the stream
+ *   RLE_STATUS_MISALIGNED  the stream or the new content is not 16-byte aligned, or
+ *                          d_cap[i] < rle_append_slot_bytes(C, A) (as the decode treats cap < U)
+ *   RLE_STATUS_TOOLARGE    rle_append_slot_bytes(C, A) == 0
+ * Parity (as include/rle_fileops.h states for RLEappend): for encoder output the result is byte-
+ * identical to the reference composition RLEcompress(RLEdecompress(y) ‖ new).  A hand-made stream that
+ * passes the scan keeps its non-canonical prefix: "aa2aa2" + "a" gives "aa2" ‖ encode("aaa") =
+ * "aa2aa3", where the reference composition re-encodes all of it to "aa5". */
+int rle_append_batch_device(void* d_streams, const uint64_t* d_off, uint64_t* d_len, const uint64_t* d_cap,
+                            uint64_t* d_ulen, uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
+                            const uint64_t* d_new_len, uint32_t* d_status, uint32_t n, void* stream);
 
 /* Diagnostic builds only (RLE_STAMPS=1, never the product library): per-segment decode cycle sums
  * over all waves: [tile wait, scan, scatter, flush reads, flush fill, flush store, flush re-zero,
