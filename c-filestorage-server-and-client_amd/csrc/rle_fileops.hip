@@ -10,11 +10,12 @@
 // Only the final run's remainder r has to be known; the old stream's tokens before it are kept.
 // The second half of the file is the same append on streams that stay in device memory, without
 // decoding them: the tail scan and the append in place (rle_tail_batch_device,
-// rle_append_batch_device).
+// rle_append_batch_device), and the append's segmented form for large new content
+// (rle_append_batch_device_seg: several waves per file, on the segmented encode's device code).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rle_device.h"
+#include "rle_seg_device.h"
 #include "rle_mi355x.h"
 
 namespace rle {
@@ -293,6 +294,200 @@ __global__ __launch_bounds__(kFileBlock) void append_kernel(uint8_t* streams, co
     }
 }
 
+// ================================================================ segmented append
+// rle_append_batch_device_seg: the same append with several waves per file, for new content that is
+// large next to the batch (one wave walks a 1 MiB append tile after tile while the chip idles).  The
+// new bytes are cut into the segmented encode's segments (seg_count over new_len; the plan and map
+// launches of csrc/rle_segmented.hip) and go through its summary, scan and write, in the virtual
+// coordinates of append_kernel: 16 head positions that are never read, then the new bytes.  What
+// differs from an encode is the state entering a file's first segment (tests/append_seg_model.py):
+//   entry    one lane per file makes append_kernel's checks before anything is stored and records
+//            c, r, e (the leading new bytes that extend the final token), vs (16, or 0 for an empty
+//            stream, which is a plain encode), t, the slot bound and the refusal status;
+//   summary  the first segment's previous byte is the recorded c, not src[p0 - 1];
+//   scan     the carry is seeded with the run start 16 - r and the output offset behind the final
+//            token; the wave rewrites that token when e > 0 and writes the file's new length, decoded
+//            length, tail word and status;
+//   write    offsets from the plan, entering values from the entry record: d_len and d_tail are
+//            outputs of the scan by then and are never read again.
+// Dependencies cross kernel boundaries only: no look-back, no ticket, nothing waits.
+constexpr u32 kEntryBlock = 256;
+struct AppEntry {
+    u32 c, r, e, vs, bad, t, need;
+};
+__device__ __forceinline__ AppEntry app_entry(const uint4* entry, u32 b) {
+    const uint4 v = entry[b];
+    const u32 x = uniform(v.x);
+    return AppEntry{x & 0xFFu, (x >> 8) & 0xFFu, (x >> 16) & 0xFFu, x >> 24, uniform(v.y), uniform(v.z), uniform(v.w)};
+}
+
+__global__ __launch_bounds__(kEntryBlock) void append_seg_entry_kernel(const uint8_t* __restrict__ streams,
+                                                                       const uint64_t* __restrict__ off,
+                                                                       const uint64_t* __restrict__ len,
+                                                                       const uint64_t* __restrict__ cap,
+                                                                       const uint64_t* __restrict__ tail,
+                                                                       const uint8_t* __restrict__ newb,
+                                                                       const uint64_t* __restrict__ new_off,
+                                                                       const uint64_t* __restrict__ new_len, u32 n,
+                                                                       uint4* __restrict__ entry) {
+    const u32 b = blockIdx.x * kEntryBlock + threadIdx.x;
+    if (b >= n) return;
+    const uint64_t C64 = len[b], A64 = new_len[b], cp = cap[b], w = tail[b];
+    const uint8_t* dst = streams + off[b];
+    const uint8_t* nw = newb + new_off[b];
+    const uint64_t need = append_slot_bytes(C64, A64);
+    u32 bad = need ? 0u : RLE_STATUS_TOOLARGE;
+    if ((((uintptr_t)dst | (uintptr_t)nw) & 15u) || (need && cp < need)) bad |= RLE_STATUS_MISALIGNED;
+    const u32 t = (u32)w, r = (u32)(w >> 32);
+    u32 c = 0u, e = 0u, vs = 0u;
+    if (!bad) {
+        // the tail word describes the stream's last bytes (as in append_kernel)
+        if (w == 0u) {
+            if (C64) bad = RLE_STATUS_NOTCANON;
+        } else if ((w >> 36) || r < 1u || r > 9u || C64 != (uint64_t)t + (r == 1u ? 1u : 3u)) {
+            bad = RLE_STATUS_NOTCANON;
+        } else {
+            c = dst[t];
+            if (r > 1u && (dst[t + 1u] != c || dst[t + 2u] != 0x30u + r)) bad = RLE_STATUS_NOTCANON;
+        }
+    }
+    u32 x = 0u;
+    if (!bad && C64) {
+        const u32 lim = A64 < 9u - r ? (u32)A64 : 9u - r;
+        while (e < lim && nw[e] == c) ++e;
+        vs = 16u;
+        x = c | (r << 8) | (e << 16) | (vs << 24);
+    }
+    entry[b] = make_uint4(x, bad, t, (u32)need);
+}
+
+__global__ __launch_bounds__(kSegBlock) void append_seg_summary_kernel(const uint8_t* __restrict__ newb,
+                                                                       const uint64_t* __restrict__ new_off,
+                                                                       const uint64_t* __restrict__ new_len, u32 n,
+                                                                       const u32* __restrict__ seg_first,
+                                                                       const u32* __restrict__ seg_buf, u32 maxseg,
+                                                                       u32 sb, const uint4* __restrict__ entry,
+                                                                       uint4* __restrict__ summ) {
+    __shared__ __attribute__((aligned(16))) uint8_t slots_all[kSegWaves * 2 * kSlot];
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    const uint8_t* slots = slots_all + wid * 2 * kSlot;
+    u32 total = seg_total(seg_first, n, new_len, sb);
+    total = total < maxseg ? total : maxseg;
+    for (u32 g = blockIdx.x * kSegWaves + wid; g < total; g += gridDim.x * kSegWaves) {
+        const u32 b = seg_of(seg_buf, g);
+        const u32 s0 = seg_lo(seg_first, b), nseg = seg_hi(seg_first, b, new_len, sb) - s0;
+        const AppEntry en = app_entry(entry, b);
+        const uint64_t A64 = new_len[b];
+        uint4 res = make_uint4(0u, 0u, 0u, 0u);
+        if (!en.bad && A64) {   // accepted by the entry kernel: length, alignment, tail word
+            const u32 A = (u32)A64;
+            const uint8_t* src = reinterpret_cast<const uint8_t*>((uintptr_t)(newb + new_off[b]) - en.vs);
+            u32 p0, p1;
+            seg_range(g - s0, nseg, A, sb, p0, p1);
+            res = enc_seg_summarize(src, en.vs + A, en.vs + p0, en.vs + p1, lane, slots,
+                                    SegEntry{g == s0 && en.vs != 0u, en.c});
+        }
+        if (lane == 0) summ[g] = res;
+    }
+}
+
+// one wave per file: the encode's scan from the append's entering state, and everything the file's
+// words receive
+__global__ __launch_bounds__(kSegBlock) void append_seg_scan_kernel(uint8_t* streams, const uint64_t* __restrict__ off,
+                                                                    uint64_t* len, uint64_t* ulen, uint64_t* tail,
+                                                                    const uint64_t* __restrict__ new_len,
+                                                                    uint32_t* status, u32 n,
+                                                                    const u32* __restrict__ seg_first, u32 maxseg,
+                                                                    u32 sb, const uint4* __restrict__ entry,
+                                                                    const uint4* __restrict__ summ,
+                                                                    uint2* __restrict__ plan, u32* __restrict__ bflag) {
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 b = blockIdx.x * kSegWaves + uniform(threadIdx.x / kWave);
+    if (b >= n) return;
+    const AppEntry en = app_entry(entry, b);
+    const uint64_t A64 = new_len[b];
+    const uint64_t ul = ulen ? ulen[b] : 0u;
+    const u32 s0 = seg_lo(seg_first, b), s1 = seg_hi(seg_first, b, new_len, sb);
+    const u32 bad = en.bad | (s1 > maxseg ? (u32)RLE_STATUS_TOOLARGE : 0u);
+    if (bad || A64 == 0u) {   // refused, or nothing to append: the file is left as it is
+        if (lane == 0) {
+            if (status) status[b] = bad;
+            bflag[b] = kFlagSkip;
+        }
+        return;
+    }
+    const u32 A = (u32)A64, rr = en.r + en.e;
+    uint8_t* dst = streams + off[b];
+    // entering the first segment: the final token's run c^r ends at virtual position 15, and the
+    // output goes on behind that token as it stands once the e bytes are counted into it
+    EncCarry cy{en.vs ? 17u - en.r : 0u, en.vs ? en.t + (rr == 1u ? 1u : 3u) : 0u};
+    for (u32 base = s0; base < s1; base += kWave) {
+        const u32 g = base + lane;
+        const bool valid = g < s1;
+        const uint4 sm = valid ? summ[g] : make_uint4(0u, 0u, 0u, 0u);
+        const uint2 pl = enc_seg_window(sm, valid, en.vs + (g - s0) * sb, cy);
+        if (valid) plan[g] = pl;
+    }
+    if (en.e && lane < 3u) dst[en.t + lane] = (uint8_t)(lane < 2u ? en.c : 0x30u + rr);
+    if (lane == 0) {
+        const u32 Uv = en.vs + A, frs = cy.lb1 ? cy.lb1 - 1u : 0u;   // the final run's start
+        const u32 rn = (Uv - frs - 1u) % 9u + 1u;                    // the new final token's count
+        len[b] = cy.off;
+        tail[b] = (uint64_t)(cy.off - (rn == 1u ? 1u : 3u)) | ((uint64_t)rn << 32);
+        if (ulen) ulen[b] = ul + A;
+        if (status) status[b] = RLE_STATUS_OK;
+        bflag[b] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(kSegBlock) void append_seg_write_kernel(uint8_t* streams, const uint64_t* __restrict__ off,
+                                                                     const uint8_t* __restrict__ newb,
+                                                                     const uint64_t* __restrict__ new_off,
+                                                                     const uint64_t* __restrict__ new_len, u32 n,
+                                                                     const u32* __restrict__ seg_first,
+                                                                     const u32* __restrict__ seg_buf, u32 maxseg,
+                                                                     u32 sb, const uint4* __restrict__ entry,
+                                                                     const uint2* __restrict__ plan,
+                                                                     const u32* __restrict__ bflag,
+                                                                     const uint4* __restrict__ summ) {
+    __shared__ __attribute__((aligned(16))) uint8_t slots_all[kSegWaves * 2 * kSlot];
+    __shared__ __attribute__((aligned(16))) uint8_t stage_all[kSegWaves * kEncStage];
+    __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];   // enc_tile_fast's selectors
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    uint8_t* stage = stage_all + wid * kEncStage;
+    const uint8_t* slots = slots_all + wid * 2 * kSlot;
+    for (u32 k = threadIdx.x; k < kInsWaveWords; k += kSegBlock) elut[k] = kEncInsLut.s[k];
+    __syncthreads();
+    u32 total = seg_total(seg_first, n, new_len, sb);
+    total = total < maxseg ? total : maxseg;
+    for (u32 g0 = blockIdx.x * kSegWaves + wid; g0 < total; g0 += gridDim.x * kSegWaves) {
+        const u32 g = total - 1u - g0;   // (last-summarised first, as enc_seg_write_kernel)
+        const uint2 pl = plan[g];
+        const uint4 sm = summ[g];
+        const u32 b = seg_of(seg_buf, g);
+        if (uniform(bflag[b])) continue;
+        const AppEntry en = app_entry(entry, b);
+        const u32 s0 = seg_lo(seg_first, b), nseg = seg_hi(seg_first, b, new_len, sb) - s0;
+        const u32 A = (u32)new_len[b];
+        const uint8_t* src = reinterpret_cast<const uint8_t*>((uintptr_t)(newb + new_off[b]) - en.vs);
+        uint8_t* dst = streams + off[b];
+        u32 p0, p1;
+        seg_range(g - s0, nseg, A, sb, p0, p1);
+        p0 += en.vs;
+        p1 += en.vs;
+        // no run boundary in the segment: for a file's first segment too (the new bytes only
+        // continue the stored run), but never position 0 of an empty stream's encode
+        if (p0 > 0u && uniform(sm.y) == 0u && uniform(sm.x) == p1 - p0) {
+            enc_seg_uniform(src, dst, en.vs + A, p0, p1, uniform(pl.x), uniform(pl.y), lane);
+            continue;
+        }
+        enc_seg_write(src, dst, en.vs + A, p0, p1, uniform(pl.x), uniform(pl.y), lane, slots, stage, elut,
+                      SegEntry{g == s0 && en.vs != 0u, en.c}, en.need);
+    }
+}
+
 }  // namespace rle
 
 extern "C" size_t rle_append_slot_bytes(uint64_t C, uint64_t A) { return (size_t)rle::append_slot_bytes(C, A); }
@@ -315,5 +510,66 @@ extern "C" int rle_append_batch_device(void* d_streams, const uint64_t* d_off, u
     hipLaunchKernelGGL(rle::append_kernel, dim3((n + rle::kFileWaves - 1u) / rle::kFileWaves), dim3(rle::kFileBlock), 0,
                        (hipStream_t)stream, (uint8_t*)d_streams, d_off, d_len, d_cap, d_ulen, d_tail,
                        (const uint8_t*)d_new, d_new_off, d_new_len, d_status, n);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+
+// The segmented encode's carve-up of the workspace, then one 16-byte entry record per file.
+namespace {
+struct AppSegShape {
+    rle::SegShape seg;
+    uint4* entry;
+    size_t bytes;
+};
+AppSegShape append_seg_shape(char* base, uint32_t n, uint64_t total, int ncu) {
+    AppSegShape a;
+    a.seg = rle::seg_shape(base, n, total, ncu);
+    const size_t o = (a.seg.bytes + 255u) & ~(size_t)255u;
+    a.entry = reinterpret_cast<uint4*>(base + o);
+    a.bytes = o + ((sizeof(uint4) * (size_t)n + 255u) & ~(size_t)255u);
+    return a;
+}
+}  // namespace
+
+extern "C" size_t rle_append_seg_workspace_bytes(uint32_t n, uint64_t total_new_bytes) {
+    int ncu = 0;
+    if (rle::seg_device_cus(&ncu) != RLE_OK) ncu = 0;
+    return append_seg_shape(nullptr, n, total_new_bytes, ncu).bytes;
+}
+
+extern "C" int rle_append_batch_device_seg(void* d_streams, const uint64_t* d_off, uint64_t* d_len,
+                                           const uint64_t* d_cap, uint64_t* d_ulen, uint64_t* d_tail,
+                                           const void* d_new, const uint64_t* d_new_off, const uint64_t* d_new_len,
+                                           uint32_t* d_status, uint32_t n, uint64_t total_new_bytes,
+                                           void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_streams || !d_off || !d_len || !d_cap || !d_tail || !d_new || !d_new_off || !d_new_len || !d_workspace)
+        return RLE_E_INVAL;
+    // (the device query only picks the segment length, 256 CUs without a device: the workspace
+    // check below is decided before anything is launched)
+    int ncu = 0;
+    const int have = rle::seg_device_cus(&ncu);
+    const AppSegShape w = append_seg_shape(static_cast<char*>(d_workspace), n, total_new_bytes, have == RLE_OK ? ncu : 0);
+    if (workspace_bytes < w.bytes) return RLE_E_INVAL;
+    if (have != RLE_OK) return have;
+    const hipStream_t s = (hipStream_t)stream;
+    const rle::SegShape& sh = w.seg;
+    uint8_t* streams = (uint8_t*)d_streams;
+    const uint8_t* newb = (const uint8_t*)d_new;
+    // one file: no plan / map launches, the kernels take its segments from its new length
+    const bool one = n == 1u;
+    uint32_t* const seg_first = one ? nullptr : sh.seg_first;
+    uint32_t* const seg_buf = one ? nullptr : sh.seg_buf;
+    if (!one) rle::seg_launch_plan_map(d_new_len, n, sh, s);
+    hipLaunchKernelGGL(rle::append_seg_entry_kernel, dim3((n + rle::kEntryBlock - 1u) / rle::kEntryBlock),
+                       dim3(rle::kEntryBlock), 0, s, streams, d_off, d_len, d_cap, d_tail, newb, d_new_off, d_new_len, n,
+                       w.entry);
+    hipLaunchKernelGGL(rle::append_seg_summary_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, newb, d_new_off,
+                       d_new_len, n, seg_first, seg_buf, sh.maxseg, sh.sb, w.entry, sh.summ);
+    hipLaunchKernelGGL(rle::append_seg_scan_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, streams,
+                       d_off, d_len, d_ulen, d_tail, d_new_len, d_status, n, seg_first, sh.maxseg, sh.sb, w.entry,
+                       sh.summ, sh.plan, sh.bflag);
+    hipLaunchKernelGGL(rle::append_seg_write_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, streams, d_off, newb,
+                       d_new_off, d_new_len, n, seg_first, seg_buf, sh.maxseg, sh.sb, w.entry, sh.plan, sh.bflag,
+                       sh.summ);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }

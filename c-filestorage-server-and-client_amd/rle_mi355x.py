@@ -112,6 +112,10 @@ def lib():
     L.rle_tail_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp]
     L.rle_append_batch_device.restype = ctypes.c_int
     L.rle_append_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+    L.rle_append_seg_workspace_bytes.restype = sz
+    L.rle_append_seg_workspace_bytes.argtypes = [u32, u64]
+    L.rle_append_batch_device_seg.restype = ctypes.c_int
+    L.rle_append_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, sz, vp]
     L.rle_mi355x_set_coop_mode.restype = ctypes.c_int
     L.rle_mi355x_set_coop_mode.argtypes = [ctypes.c_int]
     u32p = ctypes.POINTER(u32)
@@ -408,6 +412,35 @@ def append_batch(d_streams, off, length, cap, ulen, d_new, new_off, new_len, sta
                                        _stream_ptr(stream))
     if rc != RLE_OK:
         raise RLEError(f"rle_append_batch_device failed: {rc}")
+    return tail
+
+
+def append_seg_workspace(n: int, total_new_bytes: int, device=None):
+    """A device workspace for append_batch_seg (caller-owned, reusable across calls on one stream)."""
+    import torch
+    nb = int(lib().rle_append_seg_workspace_bytes(n, int(total_new_bytes)))
+    return torch.empty(nb + 256, dtype=torch.uint8, device=device if device is not None else "cuda")
+
+
+def append_batch_seg(d_streams, off, length, cap, ulen, d_new, new_off, new_len, status=None, total_new_bytes=None,
+                     workspace=None, tail=None, stream=None):
+    """rle_append_batch_device_seg: append_batch with several waves per file, for new content that is
+    large next to the batch.  total_new_bytes (>= the sum of new_len; default: that sum) sizes the
+    segment tables; workspace: from append_seg_workspace (default: a fresh one).  Returns the tail
+    tensor, as append_batch does."""
+    n = off.numel()
+    if tail is None:
+        import torch
+        tail = torch.zeros(n, dtype=torch.int64, device=d_streams.device)
+        tail_batch(d_streams, off, length, tail, None, None, stream)
+    total = int(new_len.sum().item()) if total_new_bytes is None else int(total_new_bytes)
+    ws = workspace if workspace is not None else append_seg_workspace(n, total, d_streams.device)
+    wp, wn = _ws_ptr(ws)
+    rc = lib().rle_append_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen), _ptr(tail),
+                                           _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(status), n, total, wp, wn,
+                                           _stream_ptr(stream))
+    if rc != RLE_OK:
+        raise RLEError(f"rle_append_batch_device_seg failed: {rc}")
     return tail
 
 

@@ -232,6 +232,33 @@ int rle_append_batch_device(void* d_streams, const uint64_t* d_off, uint64_t* d_
                             uint64_t* d_ulen, uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
                             const uint64_t* d_new_len, uint32_t* d_status, uint32_t n, void* stream);
 
+/* The same append with several waves per file ("segmented form"): each file's new
+ * bytes are cut into the segments of rle_encode_batch_device_seg (rle_seg_segment_bytes(
+ * total_new_bytes) bytes each, counted over d_new_len) and go through its summary, scan and write
+ * launches, the first segment entered with the state the append carries (c, r, the offset behind
+ * the final token), every later one as an encode segment.  Arguments, accepted and refused cases,
+ * status bits and results are those of rle_append_batch_device, byte for byte, plus:
+ *   total_new_bytes  >= the sum of the n new lengths (sizes the segment tables; a file whose
+ *                    segments do not fit gets RLE_STATUS_TOOLARGE and is left untouched)
+ *   d_workspace      caller-owned device memory of at least rle_append_seg_workspace_bytes(n,
+ *                    total_new_bytes) bytes (the encode's tables and one 16-byte entry record per
+ *                    file), 256-byte aligned, not used by another launch in flight
+ * Decided on the host before anything is launched: n == 0 is RLE_OK; a NULL d_streams, d_off, d_len,
+ * d_cap, d_tail, d_new, d_new_off, d_new_len or d_workspace, or workspace_bytes below that size, is
+ * RLE_E_INVAL.
+ * rle_append_batch_device never routes here: the caller picks the form.  Use this one when the new
+ * content is large next to the batch: one big write, or a batch with files of tens of KiB and more.
+ * Measured on one MI355X (profiles/append_seg.json), one-wave against segmented: one
+ * 1 MiB append 838-1579 us against 22-23 us, 64 of them 876-1628 us against 72-97 us, one 64 KiB append
+ * 57-103 us against 20 us; 4096 appends of 4 KiB 17-23 us against 45-50 us, where the one-wave form
+ * wins.  The crossover lies between a few KiB and tens of KiB of new content per file.
+ * The tail scan has no segmented form, and RLEappend (include/rle_fileops.h) does not use this one. */
+size_t rle_append_seg_workspace_bytes(uint32_t n, uint64_t total_new_bytes);
+int rle_append_batch_device_seg(void* d_streams, const uint64_t* d_off, uint64_t* d_len, const uint64_t* d_cap,
+                                uint64_t* d_ulen, uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
+                                const uint64_t* d_new_len, uint32_t* d_status, uint32_t n,
+                                uint64_t total_new_bytes, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Diagnostic builds only (RLE_STAMPS=1, never the product library): per-segment decode cycle sums
  * over all waves: [tile wait, scan, scatter, flush reads, flush fill, flush store, flush re-zero,
  * move/drain/finish, waves]; RLE_E_INVAL otherwise. */
