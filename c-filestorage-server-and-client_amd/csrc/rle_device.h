@@ -449,6 +449,8 @@ struct EncState {
     u32 head;       // leading bytes of the first stored chunk that belong to the previous segment
     bool wt;        // write-through output stores (vstore)
     Stamps sp;      // diagnostic builds only
+    bool onev = true;   // the next step tries the single-value test (enc_span_test): a buffer's first
+                        // step and the step after a run
 };
 
 // Positions are absolute in the buffer.  Tokens start only below Uo (the end of the positions this
@@ -809,6 +811,67 @@ __device__ __forceinline__ u32 enc_tile_run(const EncAn& a, u32 pos, u32 lane, u
     st.prev_top = readlane(a.top, kLast);
     const u32 i63 = readlane(a.incl, kLast);
     st.rs = i63 > st.rs ? i63 : st.rs;
+    st.onev = true;
+    return 1u;
+}
+
+// ---------------------------------------------------------------- single-value spans, before the analysis
+// The boundary analysis of a tile that is one run costs what a literal tile's does (the SWAR
+// compares, four v_dot4, the neighbour exchange and the whole max-scan: ~190 VALU per zero tile,
+// profiles/r7_before.md).  A step of 1024-byte tiles (k64) first tests whether its bytes below U --
+// tile A, then tile B when kTwo -- all equal its first byte: each lane XORs its dwords with that
+// byte, one ballot.  On a hit the span goes out through enc_run_emit, clipped at U when it holds
+// the buffer's end (its last token then takes its own count, a lone byte when that is 1, exactly
+// as the general path writes it; only whole chunks are stored, so nothing past C), with the state
+// the analysis would have left: the run's start from the byte before the span, the run bytes past
+// it (ext) from the 8 lookahead bytes.  Tried only while st.onev (EncState), so literal data pays
+// for it once per buffer.  enc_span_test returns whether the span is one value (sp: what to emit).
+__device__ __forceinline__ u32 enc_ne_bytes(const u32x4 c, u32 vv, u32 nl) {   // != 0: one of the lane's first nl bytes is not v
+    const u32 bits = 8u * nl;   // 0..128
+    return ((c.x ^ vv) & lowmask(bits)) | (bits > 32u ? (c.y ^ vv) & lowmask(bits - 32u) : 0u) |
+           (bits > 64u ? (c.z ^ vv) & lowmask(bits - 64u) : 0u) | (bits > 96u ? (c.w ^ vv) & lowmask(bits - 96u) : 0u);
+}
+struct EncSpan {
+    u32 end, rs, ext, v;   // the span's end (<= U), its run's start, the run bytes past it, its byte
+};
+template <bool kTwo>
+__device__ __forceinline__ bool enc_span_test(const u32x4 curA, const u32x4 curB, const uint2 look, u32 pos, u32 U,
+                                              u32 lane, const EncState& st, EncSpan& sp) {
+    constexpr u32 kSpan = kTwo ? 2u * kEncStep : kEncStep;
+    const u32 end = pos + kSpan < U ? pos + kSpan : U;   // (pos < U: the tile exists)
+    // lane 0's first 8 bytes on the scalar unit: literal data leaves here
+    const u32 w0 = readlane(curA.x, 0), w1 = readlane(curA.y, 0);
+    const u32 v = w0 & 0xFFu, vv = v * 0x01010101u;
+    if (pos + 8u <= U && (w0 != vv || w1 != vv)) return false;
+    const u32x4 last = kTwo ? curB : curA;
+    u32 ne = kTwo ? (curA.x ^ vv) | (curA.y ^ vv) | (curA.z ^ vv) | (curA.w ^ vv) : 0u;
+    if (end == pos + kSpan) {
+        ne |= (last.x ^ vv) | (last.y ^ vv) | (last.z ^ vv) | (last.w ^ vv);
+    } else {   // the buffer's last tile: only its bytes below U
+        const u32 p0 = pos + kSpan - kEncStep + 16u * lane;
+        ne |= enc_ne_bytes(last, vv, p0 < U ? (U - p0 < 16u ? U - p0 : 16u) : 0u);
+    }
+    if (__builtin_amdgcn_ballot_w64(ne != 0u)) return false;
+    // run bytes past the span: the leading lookahead bytes that equal v, below U
+    u32 ext = 0;
+    if (end < U) {
+        const u32 q0 = uniform(look.x) ^ vv, q1 = uniform(look.y) ^ vv;
+        ext = q0 ? (u32)__builtin_ctz(q0) >> 3 : q1 ? 4u + ((u32)__builtin_ctz(q1) >> 3) : 8u;
+        ext = ext < U - end ? ext : U - end;
+    }
+    sp = EncSpan{end, (pos != 0u && (st.prev_top >> 24) == v) ? st.rs : pos, ext, v};
+    return true;
+}
+// The span's output and the state after it.  Returns the store instructions issued.
+__device__ __forceinline__ u32 enc_span_emit(const EncSpan& sp, u32 pos, u32 lane, uint8_t* stage, u32x4 rso,
+                                             EncState& st) {
+    st.prev_top = sp.v << 24;
+    st.rs = sp.rs;
+    st.onev = true;
+    // a short last span may hold no token start: its bytes belong to the token before it, whose
+    // count already took them from its lookahead
+    if (pos + (9u - (pos - sp.rs) % 9u) % 9u >= sp.end) return 0u;
+    enc_run_emit(pos, sp.end - pos, sp.rs, sp.ext, sp.v, lane, stage, rso, st);
     return 1u;
 }
 
@@ -919,7 +982,7 @@ __device__ __forceinline__ u32 enc_tile_an(EncAn an, const uint2 look, u32 pos, 
     RLE_STAMP(st.sp, 5);   // partial-chunk move, state
     return rounds;
 }
-template <bool k64, bool kFast = false>
+template <bool k64, bool kFast = false, bool kOne = false>
 __device__ __forceinline__ u32 enc_tile(const uint8_t* cslot, const Refill& next, u32 pos, u32 Ud, u32 Uo,
                                         u32 lane, uint8_t* stage, uint8_t* dst, u32x4 rso, EncState& st,
                                         const EncK& kc, const u32* elut = nullptr) {
@@ -927,6 +990,13 @@ __device__ __forceinline__ u32 enc_tile(const uint8_t* cslot, const Refill& next
     const u32x4 cur = *reinterpret_cast<const u32x4*>(cslot + 16u * lane);
     const uint2 look = k64 ? *reinterpret_cast<const uint2*>(cslot + kSlot) : uint2{0u, 0u};
     next();   // the slot is free once read
+    if constexpr (kOne && k64 && kFast) {   // (a whole buffer's walk: Uo == Ud)
+        if (!st.head && st.onev) {
+            EncSpan sp;
+            if (enc_span_test<false>(cur, cur, look, pos, Ud, lane, st, sp)) return enc_span_emit(sp, pos, lane, stage, rso, st);
+        }
+    }
+    st.onev = false;
     const EncAn an = enc_analyze_bounds<k64>(cur, look, pos, Ud, Uo, lane, st.prev_top, kc);
     return enc_tile_an<k64, kFast>(an, look, pos, Ud, Uo, lane, stage, dst, rso, st, kc, elut);
 }
@@ -1032,7 +1102,7 @@ __device__ __forceinline__ void enc_lit_store_b(const EncLit& r, u32 base, u32 o
 
 // Two 1024-byte tiles (k64 walks: buffers up to 16 KiB) at pos and pos + 1024; slot A holds the
 // first, slot B the second.  Returns the store instructions issued after the refills.
-template <bool kFast>
+template <bool kFast, bool kOne = false>
 __device__ __forceinline__ u32 enc_pair(const uint8_t* slotA, const uint8_t* slotB, const Refill& nxA,
                                         const Refill& nxB, u32 pos, u32 U, u32 lane, uint8_t* stage, uint8_t* dst,
                                         u32x4 rso, EncState& st, const EncK& kc, const u32* elut) {
@@ -1043,24 +1113,29 @@ __device__ __forceinline__ u32 enc_pair(const uint8_t* slotA, const uint8_t* slo
     nxA();
     nxB();
     const u32 pos1 = pos + kEncStep;
-    const EncAn a0 = enc_analyze_bounds<true>(curA, lookA, pos, U, U, lane, st.prev_top, kc);
-    // the byte before tile 1: tile 0's last byte (lane 63's top), from the data
-    const EncAn a1 = enc_analyze_bounds<true>(curB, lookB, pos1, U, U, lane, readlane(curA.w & 0xFF000000u, 63), kc);
-    if (kFast && !st.head) {
-        const bool last1 = pos1 + kEncStep >= U;   // tile 1 is the buffer's last tile
-        // run pair: both tiles one run (tile 1's first byte continues tile 0's last)
-        if (!last1) {
+    const bool last1 = pos1 + kEncStep >= U;   // tile 1 is the buffer's last tile
+    // one run over both tiles: found by the single-value test ahead of the analysis (kOne), else
+    // from the analysis (a boundary at most at the first byte; not the buffer's last pair)
+    EncSpan sp;
+    bool run = kOne && kFast && !st.head && st.onev && enc_span_test<true>(curA, curB, lookB, pos, U, lane, st, sp);
+    st.onev = false;
+    EncAn a0, a1;
+    if (!run) {
+        a0 = enc_analyze_bounds<true>(curA, lookA, pos, U, U, lane, st.prev_top, kc);
+        // the byte before tile 1: tile 0's last byte (lane 63's top), from the data
+        a1 = enc_analyze_bounds<true>(curB, lookB, pos1, U, U, lane, readlane(curA.w & 0xFF000000u, 63), kc);
+        if (kFast && !st.head && !last1) {
             const bool brk = (a0.B & (lane == 0u ? 0xFFFEu : 0xFFFFu)) != 0u || a1.B != 0u;
             if (!__builtin_amdgcn_ballot_w64(brk)) {
-                const u32 rs = (readlane(a0.B, 0) & 1u) ? pos : st.rs;
-                const u32 ext = (u32)__builtin_ctz((readlane(a1.B24, 63) >> 16) | 0x100u);
-                enc_run_emit(pos, 2u * kEncStep, rs, ext, readlane(a0.w[0], 0) & 0xFFu, lane, stage, rso, st);
-                st.prev_top = readlane(a1.top, 63);
-                const u32 i63 = readlane(a1.incl, 63);
-                st.rs = i63 > st.rs ? i63 : st.rs;
-                return 1u;
+                // (the run's start is the pair's first byte or st.rs, not tile 1's last boundary alone)
+                sp = EncSpan{pos + 2u * kEncStep, (readlane(a0.B, 0) & 1u) ? pos : st.rs,
+                             (u32)__builtin_ctz((readlane(a1.B24, 63) >> 16) | 0x100u), readlane(a0.w[0], 0) & 0xFFu};
+                run = true;
             }
         }
+    }
+    if (run) return enc_span_emit(sp, pos, lane, stage, rso, st);
+    if (kFast && !st.head) {
         // literal pair
         const u32 vm1 = last1 ? a1.validm : 0xFFFFu;
         const bool rej = enc_lit_reject(a0, 0xFFFFu) || enc_lit_reject(a1, vm1);

@@ -122,16 +122,19 @@ __global__ __launch_bounds__(kEncBlock) void encode_kernel(const uint8_t* __rest
     tl_mark(b, 1, lane);
     // 1024-byte tiles where they save a tile, up to kEncSmall (rle_device.h, enc_tile<true>)
     if (enc_ntiles_for(U) < ntiles_for(U) && U <= kEncSmall) {
-        // two tiles per step (rle_device.h enc_pair)
+        // two tiles per step (rle_device.h enc_pair); the single-value test ahead of the analysis
+        // (enc_span_test) in the small-batch instantiation only (kWtMode 1: at most one residency
+        // round): with it the kernel takes 75 VGPRs instead of 72, a wave per SIMD less on large
+        // batches (16384 x 64 KiB encode +2.6 %, profiles/r7_items_ab.md)
         walk_pairs<kEncStep, true>(rsi, 0u, RLE_NOWALK ? 0u : enc_ntiles_for(U), lane, slots,
                    [&](u32 t, const uint8_t* sa, const uint8_t* sb, const Refill& na, const Refill& nb) {
                        tl_mark(b, 2u + t, lane);
                        tl_mark(b, 3u + t, lane);
-                       return enc_pair<true>(sa, sb, na, nb, t * kEncStep, U, lane, stage, dst, rso, st, kc, elut);
+                       return enc_pair<true, kWtMode == 1u>(sa, sb, na, nb, t * kEncStep, U, lane, stage, dst, rso, st, kc, elut);
                    },
                    [&](u32 t, const uint8_t* cs, const Refill& nx) {
                        tl_mark(b, 2u + t, lane);
-                       return enc_tile<true, true>(cs, nx, t * kEncStep, U, U, lane, stage, dst, rso, st, kc, elut);
+                       return enc_tile<true, true, kWtMode == 1u>(cs, nx, t * kEncStep, U, U, lane, stage, dst, rso, st, kc, elut);
                    });
     } else {
         auto tile = [&](u32 t, const uint8_t* cs, const Refill& nx) {
