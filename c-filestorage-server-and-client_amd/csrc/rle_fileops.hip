@@ -297,19 +297,23 @@ __global__ __launch_bounds__(kFileBlock) void append_kernel(uint8_t* streams, co
 // ================================================================ segmented append
 // rle_append_batch_device_seg: the same append with several waves per file, for new content that is
 // large next to the batch (one wave walks a 1 MiB append tile after tile while the chip idles).  The
-// new bytes are cut into the segmented encode's segments (seg_count over new_len; the plan and map
-// launches of csrc/rle_segmented.hip) and go through its summary, scan and write, in the virtual
-// coordinates of append_kernel: 16 head positions that are never read, then the new bytes.  What
-// differs from an encode is the state entering a file's first segment (tests/append_seg_model.py):
+// new bytes are cut into the segmented encode's segments (seg_count over new_len; the prologue and
+// the plan and map launches of csrc/rle_segmented.hip) and go through its summary and write passes
+// themselves (enc_seg_summary_pass, enc_seg_write_pass of rle_seg_device.h, which the encode's
+// kernels call too), in the virtual coordinates of append_kernel: 16 head positions that are never
+// read, then the new bytes.  What differs from an encode is the state entering a file's first
+// segment (tests/append_seg_model.py), and all of it reaches the shared passes through the view of
+// a file that app_view makes from the entry record:
 //   entry    one lane per file makes append_kernel's checks before anything is stored and records
 //            c, r, e (the leading new bytes that extend the final token), vs (16, or 0 for an empty
 //            stream, which is a plain encode), t, the slot bound and the refusal status;
-//   summary  the first segment's previous byte is the recorded c, not src[p0 - 1];
-//   scan     the carry is seeded with the run start 16 - r and the output offset behind the final
-//            token; the wave rewrites that token when e > 0 and writes the file's new length, decoded
-//            length, tail word and status;
-//   write    offsets from the plan, entering values from the entry record: d_len and d_tail are
-//            outputs of the scan by then and are never read again.
+//   summary  the first segment's previous byte is the recorded c, not src[p0 - 1] (the view's entry);
+//   scan     the append's own kernel: the encode's window (enc_seg_window) with the carry seeded
+//            with the run start 16 - r and the output offset behind the final token; the wave
+//            rewrites that token when e > 0 and writes the file's new length, decoded length, tail
+//            word and status;
+//   write    offsets from the plan, entering values and the output bound from the view: d_len and
+//            d_tail are outputs of the scan by then and are never read again.
 // Dependencies cross kernel boundaries only: no look-back, no ticket, nothing waits.
 constexpr u32 kEntryBlock = 256;
 struct AppEntry {
@@ -319,6 +323,19 @@ __device__ __forceinline__ AppEntry app_entry(const uint4* entry, u32 b) {
     const uint4 v = entry[b];
     const u32 x = uniform(v.x);
     return AppEntry{x & 0xFFu, (x >> 8) & 0xFFu, (x >> 16) & 0xFFu, x >> 24, uniform(v.y), uniform(v.z), uniform(v.w)};
+}
+// File b as the encode's passes see it (streams: the write pass only): the virtual buffer of vs head
+// positions and the new bytes, its first segment entered with the stored stream's final byte c, the
+// output bounded by the slot; it takes part when the entry kernel accepted it (length, alignment,
+// tail word) and there is something to append.
+__device__ __forceinline__ EncView app_view(const uint4* entry, uint8_t* streams, const uint64_t* off,
+                                            const uint8_t* newb, const uint64_t* new_off, const uint64_t* new_len,
+                                            u32 b) {
+    const AppEntry en = app_entry(entry, b);
+    const uint64_t A64 = new_len[b];
+    const uint8_t* src = reinterpret_cast<const uint8_t*>((uintptr_t)(newb + new_off[b]) - en.vs);
+    return EncView{src, streams ? streams + off[b] : nullptr, en.vs + (u32)A64, en.vs, SegEntry{en.vs != 0u, en.c},
+                   en.need, !en.bad && A64 != 0u};
 }
 
 __global__ __launch_bounds__(kEntryBlock) void append_seg_entry_kernel(const uint8_t* __restrict__ streams,
@@ -369,27 +386,8 @@ __global__ __launch_bounds__(kSegBlock) void append_seg_summary_kernel(const uin
                                                                        u32 sb, const uint4* __restrict__ entry,
                                                                        uint4* __restrict__ summ) {
     __shared__ __attribute__((aligned(16))) uint8_t slots_all[kSegWaves * 2 * kSlot];
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = uniform(threadIdx.x / kWave);
-    const uint8_t* slots = slots_all + wid * 2 * kSlot;
-    u32 total = seg_total(seg_first, n, new_len, sb);
-    total = total < maxseg ? total : maxseg;
-    for (u32 g = blockIdx.x * kSegWaves + wid; g < total; g += gridDim.x * kSegWaves) {
-        const u32 b = seg_of(seg_buf, g);
-        const u32 s0 = seg_lo(seg_first, b), nseg = seg_hi(seg_first, b, new_len, sb) - s0;
-        const AppEntry en = app_entry(entry, b);
-        const uint64_t A64 = new_len[b];
-        uint4 res = make_uint4(0u, 0u, 0u, 0u);
-        if (!en.bad && A64) {   // accepted by the entry kernel: length, alignment, tail word
-            const u32 A = (u32)A64;
-            const uint8_t* src = reinterpret_cast<const uint8_t*>((uintptr_t)(newb + new_off[b]) - en.vs);
-            u32 p0, p1;
-            seg_range(g - s0, nseg, A, sb, p0, p1);
-            res = enc_seg_summarize(src, en.vs + A, en.vs + p0, en.vs + p1, lane, slots,
-                                    SegEntry{g == s0 && en.vs != 0u, en.c});
-        }
-        if (lane == 0) summ[g] = res;
-    }
+    enc_seg_summary_pass(SegCut{seg_first, seg_buf, new_len, n, maxseg, sb}, summ, slots_all,
+                         [=](u32 b) { return app_view(entry, nullptr, nullptr, newb, new_off, new_len, b); });
 }
 
 // one wave per file: the encode's scan from the append's entering state, and everything the file's
@@ -453,39 +451,9 @@ __global__ __launch_bounds__(kSegBlock) void append_seg_write_kernel(uint8_t* st
                                                                      const uint4* __restrict__ summ) {
     __shared__ __attribute__((aligned(16))) uint8_t slots_all[kSegWaves * 2 * kSlot];
     __shared__ __attribute__((aligned(16))) uint8_t stage_all[kSegWaves * kEncStage];
-    __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];   // enc_tile_fast's selectors
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = uniform(threadIdx.x / kWave);
-    uint8_t* stage = stage_all + wid * kEncStage;
-    const uint8_t* slots = slots_all + wid * 2 * kSlot;
-    for (u32 k = threadIdx.x; k < kInsWaveWords; k += kSegBlock) elut[k] = kEncInsLut.s[k];
-    __syncthreads();
-    u32 total = seg_total(seg_first, n, new_len, sb);
-    total = total < maxseg ? total : maxseg;
-    for (u32 g0 = blockIdx.x * kSegWaves + wid; g0 < total; g0 += gridDim.x * kSegWaves) {
-        const u32 g = total - 1u - g0;   // (last-summarised first, as enc_seg_write_kernel)
-        const uint2 pl = plan[g];
-        const uint4 sm = summ[g];
-        const u32 b = seg_of(seg_buf, g);
-        if (uniform(bflag[b])) continue;
-        const AppEntry en = app_entry(entry, b);
-        const u32 s0 = seg_lo(seg_first, b), nseg = seg_hi(seg_first, b, new_len, sb) - s0;
-        const u32 A = (u32)new_len[b];
-        const uint8_t* src = reinterpret_cast<const uint8_t*>((uintptr_t)(newb + new_off[b]) - en.vs);
-        uint8_t* dst = streams + off[b];
-        u32 p0, p1;
-        seg_range(g - s0, nseg, A, sb, p0, p1);
-        p0 += en.vs;
-        p1 += en.vs;
-        // no run boundary in the segment: for a file's first segment too (the new bytes only
-        // continue the stored run), but never position 0 of an empty stream's encode
-        if (p0 > 0u && uniform(sm.y) == 0u && uniform(sm.x) == p1 - p0) {
-            enc_seg_uniform(src, dst, en.vs + A, p0, p1, uniform(pl.x), uniform(pl.y), lane);
-            continue;
-        }
-        enc_seg_write(src, dst, en.vs + A, p0, p1, uniform(pl.x), uniform(pl.y), lane, slots, stage, elut,
-                      SegEntry{g == s0 && en.vs != 0u, en.c}, en.need);
-    }
+    __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];
+    enc_seg_write_pass(SegCut{seg_first, seg_buf, new_len, n, maxseg, sb}, SegScanned{plan, bflag, summ}, slots_all,
+                       stage_all, elut, [=](u32 b) { return app_view(entry, streams, off, newb, new_off, new_len, b); });
 }
 
 }  // namespace rle
@@ -513,27 +481,11 @@ extern "C" int rle_append_batch_device(void* d_streams, const uint64_t* d_off, u
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }
 
-// The segmented encode's carve-up of the workspace, then one 16-byte entry record per file.
-namespace {
-struct AppSegShape {
-    rle::SegShape seg;
-    uint4* entry;
-    size_t bytes;
-};
-AppSegShape append_seg_shape(char* base, uint32_t n, uint64_t total, int ncu) {
-    AppSegShape a;
-    a.seg = rle::seg_shape(base, n, total, ncu);
-    const size_t o = (a.seg.bytes + 255u) & ~(size_t)255u;
-    a.entry = reinterpret_cast<uint4*>(base + o);
-    a.bytes = o + ((sizeof(uint4) * (size_t)n + 255u) & ~(size_t)255u);
-    return a;
-}
-}  // namespace
-
+// The workspace: the segmented encode's carve-up, then one 16-byte entry record per file.
 extern "C" size_t rle_append_seg_workspace_bytes(uint32_t n, uint64_t total_new_bytes) {
-    int ncu = 0;
-    if (rle::seg_device_cus(&ncu) != RLE_OK) ncu = 0;
-    return append_seg_shape(nullptr, n, total_new_bytes, ncu).bytes;
+    rle::SegShape sh;
+    rle::seg_prologue(nullptr, 0, n, total_new_bytes, sizeof(uint4) * (size_t)n, &sh);
+    return sh.bytes;
 }
 
 extern "C" int rle_append_batch_device_seg(void* d_streams, const uint64_t* d_off, uint64_t* d_len,
@@ -542,34 +494,25 @@ extern "C" int rle_append_batch_device_seg(void* d_streams, const uint64_t* d_of
                                            uint32_t* d_status, uint32_t n, uint64_t total_new_bytes,
                                            void* d_workspace, size_t workspace_bytes, void* stream) {
     if (n == 0) return RLE_OK;
-    if (!d_streams || !d_off || !d_len || !d_cap || !d_tail || !d_new || !d_new_off || !d_new_len || !d_workspace)
-        return RLE_E_INVAL;
-    // (the device query only picks the segment length, 256 CUs without a device: the workspace
-    // check below is decided before anything is launched)
-    int ncu = 0;
-    const int have = rle::seg_device_cus(&ncu);
-    const AppSegShape w = append_seg_shape(static_cast<char*>(d_workspace), n, total_new_bytes, have == RLE_OK ? ncu : 0);
-    if (workspace_bytes < w.bytes) return RLE_E_INVAL;
-    if (have != RLE_OK) return have;
+    if (!d_streams || !d_off || !d_len || !d_cap || !d_tail || !d_new || !d_new_off || !d_new_len) return RLE_E_INVAL;
+    rle::SegShape sh;
+    const size_t records = sizeof(uint4) * (size_t)n;   // one entry record per file behind the encode's tables
+    if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_new_bytes, records, &sh)) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    const rle::SegShape& sh = w.seg;
+    uint4* const entry = static_cast<uint4*>(sh.extra);
     uint8_t* streams = (uint8_t*)d_streams;
     const uint8_t* newb = (const uint8_t*)d_new;
-    // one file: no plan / map launches, the kernels take its segments from its new length
-    const bool one = n == 1u;
-    uint32_t* const seg_first = one ? nullptr : sh.seg_first;
-    uint32_t* const seg_buf = one ? nullptr : sh.seg_buf;
-    if (!one) rle::seg_launch_plan_map(d_new_len, n, sh, s);
+    rle::seg_launch_plan_map(d_new_len, n, sh, s);
     hipLaunchKernelGGL(rle::append_seg_entry_kernel, dim3((n + rle::kEntryBlock - 1u) / rle::kEntryBlock),
                        dim3(rle::kEntryBlock), 0, s, streams, d_off, d_len, d_cap, d_tail, newb, d_new_off, d_new_len, n,
-                       w.entry);
+                       entry);
     hipLaunchKernelGGL(rle::append_seg_summary_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, newb, d_new_off,
-                       d_new_len, n, seg_first, seg_buf, sh.maxseg, sh.sb, w.entry, sh.summ);
+                       d_new_len, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, entry, sh.summ);
     hipLaunchKernelGGL(rle::append_seg_scan_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, streams,
-                       d_off, d_len, d_ulen, d_tail, d_new_len, d_status, n, seg_first, sh.maxseg, sh.sb, w.entry,
+                       d_off, d_len, d_ulen, d_tail, d_new_len, d_status, n, sh.seg_first, sh.maxseg, sh.sb, entry,
                        sh.summ, sh.plan, sh.bflag);
     hipLaunchKernelGGL(rle::append_seg_write_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, streams, d_off, newb,
-                       d_new_off, d_new_len, n, seg_first, seg_buf, sh.maxseg, sh.sb, w.entry, sh.plan, sh.bflag,
+                       d_new_off, d_new_len, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, entry, sh.plan, sh.bflag,
                        sh.summ);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }

@@ -1,8 +1,11 @@
 // rle_seg_device.h — the device code of the segmented encode that more than one translation unit
-// uses: the segment cut (seg_count, seg_range), a segment's summary, the per-buffer scan window and
-// the two segment writers.  csrc/rle_segmented.hip builds the segmented codec from it, and
-// csrc/rle_fileops.hip the segmented append (rle_append_batch_device_seg), which enters a file's
-// first segment with the state an append carries and runs every later segment as the encode does.
+// uses: the segment cut (seg_count, seg_range), the persistent walk over a launch's segments
+// (seg_walk), a segment's summary, the per-buffer scan window, the two segment writers, and the
+// encode's summary and write passes over a per-buffer view (EncView).  csrc/rle_segmented.hip builds
+// the segmented codec from it, and csrc/rle_fileops.hip the segmented append
+// (rle_append_batch_device_seg), whose view enters a file's first segment with the state an append
+// carries and runs every later segment as the encode does.  The host side at the end declares the
+// launch shape and prologue that every segmented entry point shares.
 // The algebra: tests/seg_model.py, tests/append_seg_model.py.
 #pragma once
 #include "rle_device.h"
@@ -43,6 +46,51 @@ __device__ __forceinline__ u32 seg_hi(const u32* seg_first, u32 b, const uint64_
 __device__ __forceinline__ void seg_range(u32 i, u32 nseg, u32 n, u32 sb, u32& p0, u32& p1) {
     p0 = i * sb;
     p1 = (i + 1u == nseg) ? n : p0 + sb;
+}
+
+// The persistent walk of every summary and write kernel (encode, decode, append) over a launch's
+// segments: wave wid of workgroup k takes segments 4 k + wid, + 4 gridDim.x, ... below the segment
+// bound, and the body gets each one with its buffer b and that buffer's segments [s0, s0 + nseg).
+// The summaries go forward.  The writes (kWrite) go last-summarised first (memory-side cache reuse,
+// r3w), get the segment's own plan and summary words, loaded with its buffer index, not after it,
+// and the buffer's flags, and never see a segment of a buffer the scan refused (kFlagSkip).
+struct SegCut {   // the cut as the kernels are told it: tables (null for one buffer), lengths, bounds
+    const u32* seg_first;
+    const u32* seg_buf;
+    const uint64_t* len;
+    u32 n, maxseg, sb;
+};
+struct SegScanned {   // what the scan left for the write pass
+    const uint2* plan;
+    const u32* bflag;
+    const uint4* summ;
+};
+struct Seg {
+    u32 g, b, s0, nseg;
+    u32 flag;   // the write passes only, as pl and sm
+    uint2 pl;
+    uint4 sm;
+};
+template <bool kWrite, class Body>
+__device__ __forceinline__ void seg_walk(const SegCut& k, u32 wid, const SegScanned& w, Body body) {
+    u32 total = seg_total(k.seg_first, k.n, k.len, k.sb);
+    total = total < k.maxseg ? total : k.maxseg;
+    for (u32 g0 = blockIdx.x * kSegWaves + wid; g0 < total; g0 += gridDim.x * kSegWaves) {
+        Seg s{};
+        s.g = kWrite ? total - 1u - g0 : g0;
+        if (kWrite) {
+            s.pl = w.plan[s.g];
+            s.sm = w.summ[s.g];
+        }
+        s.b = seg_of(k.seg_buf, s.g);
+        if (kWrite) {
+            s.flag = uniform(w.bflag[s.b]);
+            if (s.flag & kFlagSkip) continue;
+        }
+        s.s0 = seg_lo(k.seg_first, s.b);
+        s.nseg = seg_hi(k.seg_first, s.b, k.len, k.sb) - s.s0;
+        body(s);
+    }
 }
 
 __device__ __forceinline__ u32 wave_sum(u32 x) { return readlane(wave_scan_incl(x, 0u, OpAdd()), 63); }
@@ -258,25 +306,96 @@ __device__ RLE_SEG_UNIFORM_ATTR void enc_seg_uniform(const uint8_t* src, uint8_t
     if (lane < 16u && t0 + lane < end) dst[t0 + lane] = (uint8_t)byte_at(t0 + lane - off);
 }
 
+// One buffer as the encode's summary and write passes see it.  The segmented encode and the
+// segmented append run the same two passes and differ only in this view, which each kernel makes
+// from its own arguments (view(b)): the encode's has vs = 0, no entry and the default bound; the
+// append's is a virtual buffer whose first vs positions lie in front of the new bytes and whose
+// first segment is entered with the stored stream's final byte.
+struct EncView {
+    const uint8_t* src;   // position 0 (the append: new bytes - vs, never read below vs)
+    uint8_t* dst;         // the write pass only
+    u32 U, vs;            // length, and the first position that is cut into segments
+    SegEntry en;          // entering the buffer's first segment
+    u32 need;             // the bytes of dst the stores may reach (0: U + U / 2)
+    bool live;            // the summary pass only: the buffer takes part (else its summaries are 0)
+};
+
+template <class View>
+__device__ __forceinline__ void enc_seg_summary_pass(const SegCut& k, uint4* summ, const uint8_t* slots_all, View view) {
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    const uint8_t* slots = slots_all + wid * 2 * kSlot;
+    seg_walk<false>(k, wid, SegScanned{}, [&](const Seg& s) {
+        const EncView v = view(s.b);
+        uint4 res = make_uint4(0u, 0u, 0u, 0u);
+        if (v.live) {
+            u32 p0, p1;
+            seg_range(s.g - s.s0, s.nseg, v.U - v.vs, k.sb, p0, p1);
+            res = enc_seg_summarize(v.src, v.U, v.vs + p0, v.vs + p1, lane, slots,
+                                    SegEntry{s.g == s.s0 && v.en.given, v.en.prev});
+        }
+        if (lane == 0) summ[s.g] = res;
+    });
+}
+
+// (slots_all, stage_all, elut: the kernel's LDS, kSegWaves * 2 * kSlot, kSegWaves * kEncStage bytes
+// and kInsWaveWords words, enc_tile_fast's selectors)
+template <class View>
+__device__ __forceinline__ void enc_seg_write_pass(const SegCut& k, const SegScanned& w, const uint8_t* slots_all,
+                                                   uint8_t* stage_all, u32* elut, View view) {
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    uint8_t* stage = stage_all + wid * kEncStage;
+    const uint8_t* slots = slots_all + wid * 2 * kSlot;
+    for (u32 i = threadIdx.x; i < kInsWaveWords; i += kSegBlock) elut[i] = kEncInsLut.s[i];
+    __syncthreads();
+    seg_walk<true>(k, wid, w, [&](const Seg& s) {
+        const EncView v = view(s.b);
+        u32 p0, p1;
+        seg_range(s.g - s.s0, s.nseg, v.U - v.vs, k.sb, p0, p1);
+        p0 += v.vs;
+        p1 += v.vs;
+        // no run boundary in the segment: for an append's first segment too (the new bytes only
+        // continue the stored run), but never position 0 of a buffer
+        if (p0 > 0u && uniform(s.sm.y) == 0u && uniform(s.sm.x) == p1 - p0) {
+            enc_seg_uniform(v.src, v.dst, v.U, p0, p1, uniform(s.pl.x), uniform(s.pl.y), lane);
+            return;
+        }
+        enc_seg_write(v.src, v.dst, v.U, p0, p1, uniform(s.pl.x), uniform(s.pl.y), lane, slots, stage, elut,
+                      SegEntry{s.g == s.s0 && v.en.given, v.en.prev}, v.need);
+    });
+}
+
 }  // namespace rle
 
 // ---------------------------------------------------------------- host side (csrc/rle_segmented.hip)
-// What a segmented launch over n buffers holding `total` bytes looks like: segment length, segment
-// bound, persistent grid, and the 256-byte-aligned carve-up of the caller's workspace (base may be
-// null: sizes only).  ncu <= 0 stands for a machine without a device (256 CUs).
+// What a segmented launch over n buffers holding `total` bytes looks like: CUs (256 on a machine
+// without a device), segment length, segment bound, persistent grid, and the 256-byte-aligned
+// carve-up of the caller's workspace: the tables, then `extra` bytes of the caller's own.  Every
+// pointer is null when the workspace is (sizes only).
 namespace rle {
 struct SegShape {
+    int ncu;
     uint32_t sb, maxseg, grid;
-    uint32_t* seg_first;
-    uint32_t* seg_buf;
+    uint32_t* seg_first;   // null for one buffer too: the kernels take its segments from its length
+    uint32_t* seg_buf;     // per-segment buffer index (seg_map_kernel)
     uint4* summ;
     uint2* plan;
     uint32_t* bflag;
+    uint32_t* sflag;    // single-pass variants: per-segment publication flag
+    uint4* incl;        // single-pass variants: per-segment inclusive state
+    uint32_t* ticket;   // single-pass variants: segment ticket counter
+    void* extra;
     size_t bytes;
 };
-int seg_device_cus(int* ncu);   // RLE_OK or RLE_E_HIP
-SegShape seg_shape(char* base, uint32_t n, uint64_t total, int ncu);
-// the plan and map launches over `len` (seg_first, seg_buf of the shape)
-void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hipStream_t s);
-inline uint32_t seg_buf_grid(uint32_t n) { return (n + 3u) / 4u; }   // one wave per buffer, kSegWaves per workgroup
+// The prologue of every segmented entry point, after n == 0 and the NULL checks of its own pointers:
+// the shape of this n and total over the workspace, then everything decidable on the host first
+// (RLE_E_INVAL for a NULL or short workspace), then the device query's error (RLE_E_HIP).  The size
+// queries call it without a workspace and read sh->bytes.
+int seg_prologue(void* d_workspace, size_t workspace_bytes, uint32_t n, uint64_t total, size_t extra, SegShape* sh);
+// The plan and map launches over `len` into seg_first and seg_buf of the shape; none for one buffer.
+// The single-pass variants have the plan clear their flags, ticket and per-buffer words as well.
+void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hipStream_t s,
+                         uint32_t* sflag = nullptr, uint32_t* ticket = nullptr, uint32_t* bclear = nullptr);
+inline uint32_t seg_buf_grid(uint32_t n) { return (n + kSegWaves - 1u) / kSegWaves; }   // one wave per buffer
 }  // namespace rle

@@ -81,17 +81,6 @@ __global__ __launch_bounds__(1024) void seg_plan_kernel(const uint64_t* __restri
     if (t == 1023u) seg_first[n] = part[1023];
 }
 
-// the buffer holding global segment g: seg_first[b] <= g < seg_first[b + 1] (every buffer has a
-// segment, so seg_first is strictly increasing)
-__device__ __forceinline__ u32 seg_buffer(const u32* seg_first, u32 n, u32 g) {
-    u32 lo = 0, hi = n;
-    while (hi - lo > 1u) {
-        const u32 mid = (lo + hi) >> 1;
-        if (uniform(seg_first[mid]) <= g) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 // seg_buf[g] = the buffer holding segment g, for every segment (one binary search per segment, all
 // in parallel), so the persistent summary and write waves find a segment's buffer with one load
 constexpr u32 kMapBlock = 256;
@@ -108,53 +97,25 @@ __global__ __launch_bounds__(kMapBlock) void seg_map_kernel(const u32* __restric
     }
     seg_buf[g] = lo;
 }
-// Resident segments (the single-pass kernels below): a segment of at most kResTiles tiles (segments
-// are kResTiles - 1 tiles, a buffer's last one up to 2 bytes more) is loaded
-// into the wave's LDS region once, [p0, p0 + 1008 nt + 16) in 1 KiB LDS-DMAs (range-checked: zeros
-// past the buffer), and both its summary and its output walk read it there.
-#ifndef RLE_RES_TILES
-#define RLE_RES_TILES 8
-#endif
-constexpr u32 kResTiles = RLE_RES_TILES;
-constexpr u32 kResBytes = (kResTiles * kTileStep + 16u + 1023u) & ~1023u;
-[[maybe_unused]] constexpr u32 kResStride = kResBytes;
-#ifndef RLE_RES_DEC_CHUNKS   // the resident decode's staging (chunks per wave; its region takes LDS too)
-#define RLE_RES_DEC_CHUNKS 96
-#endif
-[[maybe_unused]] constexpr u32 kResDecChunks = RLE_RES_DEC_CHUNKS;
-__device__ __forceinline__ void res_load(u32x4 rs, u32 p0, u32 nt, u32 lane, const uint8_t* region) {
-    const u32 l0 = uniform(lds_addr(region));
-    const u32 nd = uniform((nt * kTileStep + 16u + 1023u) >> 10);
-    asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh (walk_prime)
-    for (u32 k = 0; k < nd; ++k) dma_tile<true>(rs, p0 + 1024u * k + 16u * lane, l0 + 1024u * k);
-    vm_drain();
+// ================================================================ ENCODE
+// Buffer b as the passes of rle_seg_device.h see it (out: the write pass only): all of it is cut
+// into segments, no entry state, the default output bound.
+__device__ __forceinline__ EncView enc_view(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
+                                            uint8_t* out, const uint64_t* out_off, u32 b) {
+    const uint64_t U64 = in_len[b];
+    const uint8_t* src = in + in_off[b];
+    return EncView{src, out ? out + out_off[b] : nullptr, (u32)U64, 0u, SegEntry{false, 0u}, 0u,
+                   U64 > 0 && U64 <= kMaxBufferBytes && !((uintptr_t)src & 15u)};
 }
 
-// ================================================================ ENCODE
 __global__ __launch_bounds__(kSegBlock) void enc_seg_summary_kernel(const uint8_t* __restrict__ in,
                                                                     const uint64_t* __restrict__ in_off,
                                                                     const uint64_t* __restrict__ in_len, u32 n,
                                                                     const u32* __restrict__ seg_first, const u32* __restrict__ seg_buf, u32 maxseg, u32 sb,
                                                                     uint4* __restrict__ summ) {
     __shared__ __attribute__((aligned(16))) uint8_t slots_all[kSegWaves * 2 * kSlot];
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = uniform(threadIdx.x / kWave);
-    const uint8_t* slots = slots_all + wid * 2 * kSlot;
-    u32 total = seg_total(seg_first, n, in_len, sb);
-    total = total < maxseg ? total : maxseg;
-    for (u32 g = blockIdx.x * kSegWaves + wid; g < total; g += gridDim.x * kSegWaves) {
-        const u32 b = seg_of(seg_buf, g);
-        const u32 s0 = seg_lo(seg_first, b), nseg = seg_hi(seg_first, b, in_len, sb) - s0;
-        const uint64_t U64 = in_len[b];
-        const uint8_t* src = in + in_off[b];
-        uint4 res = make_uint4(0u, 0u, 0u, 0u);
-        if (U64 > 0 && U64 <= kMaxBufferBytes && !((uintptr_t)src & 15u)) {
-            u32 p0, p1;
-            seg_range(g - s0, nseg, (u32)U64, sb, p0, p1);
-            res = enc_seg_summarize(src, (u32)U64, p0, p1, lane, slots);
-        }
-        if (lane == 0) summ[g] = res;
-    }
+    enc_seg_summary_pass(SegCut{seg_first, seg_buf, in_len, n, maxseg, sb}, summ, slots_all,
+                         [=](u32 b) { return enc_view(in, in_off, in_len, nullptr, nullptr, b); });
 }
 
 // one wave per buffer: entering run start and output offset of every segment, C of the buffer
@@ -211,36 +172,9 @@ __global__ __launch_bounds__(kSegBlock) void enc_seg_write_kernel(const uint8_t*
                                                                   const uint4* __restrict__ summ) {
     __shared__ __attribute__((aligned(16))) uint8_t slots_all[kSegWaves * 2 * kSlot];
     __shared__ __attribute__((aligned(16))) uint8_t stage_all[kSegWaves * kEncStage];
-    __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];   // enc_tile_fast's selectors
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = uniform(threadIdx.x / kWave);
-    uint8_t* stage = stage_all + wid * kEncStage;
-    const uint8_t* slots = slots_all + wid * 2 * kSlot;
-    for (u32 k = threadIdx.x; k < kInsWaveWords; k += kSegBlock) elut[k] = kEncInsLut.s[k];
-    __syncthreads();
-    u32 total = seg_total(seg_first, n, in_len, sb);
-    total = total < maxseg ? total : maxseg;
-    for (u32 g0 = blockIdx.x * kSegWaves + wid; g0 < total; g0 += gridDim.x * kSegWaves) {
-        const u32 g = total - 1u - g0;
-        // (the segment's own plan and summary load with its buffer index, not after it)
-        const uint2 pl = plan[g];
-        const uint4 sm = summ[g];
-        const u32 b = seg_of(seg_buf, g);
-        if (uniform(bflag[b])) continue;
-        const u32 s0 = seg_lo(seg_first, b), nseg = seg_hi(seg_first, b, in_len, sb) - s0;
-        const u32 U = (u32)in_len[b];
-        const uint8_t* src = in + in_off[b];
-        uint8_t* dst = out + out_off[b];
-        u32 p0, p1;
-        seg_range(g - s0, nseg, U, sb, p0, p1);
-        if (p0 > 0u) {
-            if (uniform(sm.y) == 0u && uniform(sm.x) == p1 - p0) {   // no run boundary in the segment
-                enc_seg_uniform(src, dst, U, p0, p1, uniform(pl.x), uniform(pl.y), lane);
-                continue;
-            }
-        }
-        enc_seg_write(src, dst, U, p0, p1, uniform(pl.x), uniform(pl.y), lane, slots, stage, elut);
-    }
+    __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];
+    enc_seg_write_pass(SegCut{seg_first, seg_buf, in_len, n, maxseg, sb}, SegScanned{plan, bflag, summ}, slots_all,
+                       stage_all, elut, [=](u32 b) { return enc_view(in, in_off, in_len, out, out_off, b); });
 }
 
 // ================================================================ measured-slower variants
@@ -317,6 +251,121 @@ __device__ __forceinline__ u32 seg_lookback(u32 g, u32 s0, const u32* sflag, u32
     }
 }
 
+// the buffer holding global segment g: seg_first[b] <= g < seg_first[b + 1] (every buffer has a
+// segment, so seg_first is strictly increasing)
+__device__ __forceinline__ u32 seg_buffer(const u32* seg_first, u32 n, u32 g) {
+    u32 lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const u32 mid = (lo + hi) >> 1;
+        if (uniform(seg_first[mid]) <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// Resident segments (the resident single-pass kernels): a segment of at most kResTiles tiles
+// (segments are kResTiles - 1 tiles, a buffer's last one up to 2 bytes more) is loaded into the
+// wave's LDS region once, [p0, p0 + 1008 nt + 16) in 1 KiB LDS-DMAs (range-checked: zeros past the
+// buffer), and both its summary and its output walk read it there.
+#ifndef RLE_RES_TILES
+#define RLE_RES_TILES 8
+#endif
+constexpr u32 kResTiles = RLE_RES_TILES;
+constexpr u32 kResBytes = (kResTiles * kTileStep + 16u + 1023u) & ~1023u;
+constexpr u32 kResStride = kResBytes;
+#ifndef RLE_RES_DEC_CHUNKS   // the resident decode's staging (chunks per wave; its region takes LDS too)
+#define RLE_RES_DEC_CHUNKS 96
+#endif
+constexpr u32 kResDecChunks = RLE_RES_DEC_CHUNKS;
+__device__ __forceinline__ void res_load(u32x4 rs, u32 p0, u32 nt, u32 lane, const uint8_t* region) {
+    const u32 l0 = uniform(lds_addr(region));
+    const u32 nd = uniform((nt * kTileStep + 16u + 1023u) >> 10);
+    asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh (walk_prime)
+    for (u32 k = 0; k < nd; ++k) dma_tile<true>(rs, p0 + 1024u * k + 16u * lane, l0 + 1024u * k);
+    vm_drain();
+}
+
+// What the encode kernel's arguments and LDS give a single-pass wave (mem: its two DMA slots, or its
+// resident region).
+struct EncSingle {
+    const uint8_t* in;
+    const uint64_t* in_off;
+    const uint64_t* in_len;
+    uint8_t* out;
+    const uint64_t* out_off;
+    uint64_t* out_len;
+    uint32_t* status;
+    const u32* seg_first;
+    u32 maxseg, sb;
+    uint4* summ;
+    uint4* incl;
+    u32* sflag;
+    u32 lane;
+    const uint8_t* mem;
+    uint8_t* stage;
+    const u32* elut;
+};
+// Segment g of buffer b in one pass, however the wave came by it (kRes: held in LDS): summarise and
+// publish the summary, derive the entering state from the segments before it, publish the inclusive
+// state, write.
+template <bool kRes>
+__device__ __forceinline__ void enc_seg_single(const EncSingle& a, u32 g, u32 b) {
+    const u32 lane = a.lane;
+    const u32 s0 = uniform(a.seg_first[b]), s1 = uniform(a.seg_first[b + 1]), nseg = s1 - s0;
+    const uint64_t U64 = a.in_len[b];
+    const uint8_t* src = a.in + a.in_off[b];
+    uint8_t* dst = a.out + a.out_off[b];
+    u32 bad = (((uintptr_t)src | (uintptr_t)dst) & 15u) ? RLE_STATUS_MISALIGNED : 0u;
+    if (U64 > kMaxBufferBytes || s1 > a.maxseg) bad |= RLE_STATUS_TOOLARGE;
+    if (bad || U64 == 0u) {   // the buffer's segments all skip (an empty buffer is one segment)
+        if (g == s0 && lane == 0) {
+            a.out_len[b] = 0;
+            if (a.status) a.status[b] = bad;
+        }
+        return;
+    }
+    const u32 U = (u32)U64;
+    u32 p0, p1;
+    seg_range(g - s0, nseg, U, a.sb, p0, p1);
+    if (kRes) res_load(make_rsrc(src, (U + 15u) & ~15u), p0, ntiles_for(p1 - p0), lane, a.mem);
+    const uint4 sm = enc_seg_summarize<kRes>(src, U, p0, p1, lane, a.mem);
+    if (lane == 0) publish(a.summ + g, sm, a.sflag + g, kFlagAgg);
+    // the state entering this segment: the nearest published inclusive state (or the buffer's
+    // start), then the summaries after it, 64 per window
+    bool late = false;
+    EncCarry c{0u, 0u};
+    u32 lateb = 0u;
+    if (g > s0) {
+        const u32 from = seg_lookback(g, s0, a.sflag, lane, late);
+        if (from > s0) {
+            const uint4 in4 = ld_relaxed4(a.incl + (from - 1u));
+            c = EncCarry{uniform(in4.x), uniform(in4.y)};
+            lateb = uniform(in4.z);
+        }
+        for (u32 base = from; base < g; base += kWave) {
+            const u32 j = base + lane;
+            const bool valid = j < g;
+            const uint4 smj = valid ? ld_relaxed4(a.summ + j) : make_uint4(0u, 0u, 0u, 0u);
+            enc_seg_window(smj, valid, (j - s0) * a.sb, c);
+        }
+    }
+    // this segment's own step (lane 0's window entry), published as its inclusive state
+    const uint2 mine = enc_seg_window(sm, lane == 0u, p0, c);
+    lateb |= late ? RLE_STATUS_INTERNAL : 0u;
+    if (lane == 0) {
+        publish(a.incl + g, make_uint4(c.lb1, c.off, lateb, 0u), a.sflag + g, kFlagIncl);
+        // the status words were cleared by the plan launch: a late segment ORs its bit in itself
+        // (a later segment may rebuild its state from raw summaries and not carry it), and the
+        // last segment ORs what it carries, so no bit is overwritten
+        if (late && a.status) atomicOr(a.status + b, RLE_STATUS_INTERNAL);
+        if (g + 1u == s1) {   // the buffer's last segment: C and the status
+            a.out_len[b] = c.off;
+            if (lateb && a.status) atomicOr(a.status + b, lateb);
+        }
+    }
+    enc_seg_write<kRes>(src, dst, U, p0, p1, uniform(mine.x), uniform(mine.y), lane, a.mem, a.stage, a.elut);
+}
+
+// The fused kernel takes segments in ticket order and finds a segment's buffer by binary search.
 __global__ __launch_bounds__(kSegBlock) void enc_seg_fused_kernel(const uint8_t* __restrict__ in,
                                                                   const uint64_t* __restrict__ in_off,
                                                                   const uint64_t* __restrict__ in_len,
@@ -332,10 +381,10 @@ __global__ __launch_bounds__(kSegBlock) void enc_seg_fused_kernel(const uint8_t*
     __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];   // enc_tile_fast's selectors
     const u32 lane = threadIdx.x & (kWave - 1);
     const u32 wid = uniform(threadIdx.x / kWave);
-    uint8_t* stage = stage_all + wid * kEncStage;
-    const uint8_t* slots = slots_all + wid * 2 * kSlot;
     for (u32 k = threadIdx.x; k < kInsWaveWords; k += kSegBlock) elut[k] = kEncInsLut.s[k];
     __syncthreads();
+    const EncSingle a{in,   in_off, in_len, out,  out_off, out_len, status, seg_first, maxseg, sb,
+                      summ, incl,   sflag,  lane, slots_all + wid * 2 * kSlot, stage_all + wid * kEncStage, elut};
     u32 total = uniform(seg_first[n]);
     total = total < maxseg ? total : maxseg;
     for (;;) {
@@ -343,80 +392,23 @@ __global__ __launch_bounds__(kSegBlock) void enc_seg_fused_kernel(const uint8_t*
         if (lane == 0) g = atomicAdd(ticket, 1u);
         g = uniform(g);
         if (g >= total) break;
-        const u32 b = seg_buffer(seg_first, n, g);
-        const u32 s0 = uniform(seg_first[b]), s1 = uniform(seg_first[b + 1]), nseg = s1 - s0;
-        const uint64_t U64 = in_len[b];
-        const uint8_t* src = in + in_off[b];
-        uint8_t* dst = out + out_off[b];
-        u32 bad = (((uintptr_t)src | (uintptr_t)dst) & 15u) ? RLE_STATUS_MISALIGNED : 0u;
-        if (U64 > kMaxBufferBytes || s1 > maxseg) bad |= RLE_STATUS_TOOLARGE;
-        if (bad || U64 == 0u) {   // the buffer's segments all skip (an empty buffer is one segment)
-            if (g == s0 && lane == 0) {
-                out_len[b] = 0;
-                if (status) status[b] = bad;
-            }
-            continue;
-        }
-        const u32 U = (u32)U64;
-        u32 p0, p1;
-        seg_range(g - s0, nseg, U, sb, p0, p1);
-        const uint4 sm = enc_seg_summarize(src, U, p0, p1, lane, slots);
-        if (lane == 0) publish(summ + g, sm, sflag + g, kFlagAgg);
-        // the state entering this segment: the nearest published inclusive state (or the buffer's
-        // start), then the summaries after it, 64 per window
-        bool late = false;
-        EncCarry c{0u, 0u};
-        u32 lateb = 0u;
-        if (g > s0) {
-            const u32 from = seg_lookback(g, s0, sflag, lane, late);
-            if (from > s0) {
-                const uint4 in4 = ld_relaxed4(incl + (from - 1u));
-                c = EncCarry{uniform(in4.x), uniform(in4.y)};
-                lateb = uniform(in4.z);
-            }
-            for (u32 base = from; base < g; base += kWave) {
-                const u32 j = base + lane;
-                const bool valid = j < g;
-                const uint4 smj = valid ? ld_relaxed4(summ + j) : make_uint4(0u, 0u, 0u, 0u);
-                enc_seg_window(smj, valid, (j - s0) * sb, c);
-            }
-        }
-        // this segment's own step (lane 0's window entry), published as its inclusive state
-        const uint2 mine = enc_seg_window(sm, lane == 0u, p0, c);
-        const u32 rs = uniform(mine.x), off = uniform(mine.y);
-        lateb |= late ? RLE_STATUS_INTERNAL : 0u;
-        if (lane == 0) {
-            publish(incl + g, make_uint4(c.lb1, c.off, lateb, 0u), sflag + g, kFlagIncl);
-            // the status words were cleared by the plan launch: a late segment ORs its bit in itself
-            // (a later segment may rebuild its state from raw summaries and not carry it), and the
-            // last segment ORs what it carries, so no bit is overwritten
-            if (late && status) atomicOr(status + b, RLE_STATUS_INTERNAL);
-            if (g + 1u == s1) {   // the buffer's last segment: C and the status
-                out_len[b] = c.off;
-                if (lateb && status) atomicOr(status + b, lateb);
-            }
-        }
-        enc_seg_write(src, dst, U, p0, p1, rs, off, lane, slots, stage, elut);
+        enc_seg_single<false>(a, g, seg_buffer(seg_first, n, g));
     }
 }
 
-
 // ---------------------------------------------------------------- resident single-pass encode
-// SURVEY.md §5's single pass, with the segment held in LDS: a wave takes a segment by ticket and
-// loads its <= kResTiles tiles into its LDS region once, summarises them there, publishes the summary, derives its entering state with the
-// decoupled look-back of the fused kernel above, publishes its inclusive state and walks the same
-// LDS tiles again to write.  HBM sees the input once.  Progress: as in the fused kernel, a wave
-// waits only on segments of earlier tickets, whose waves are running.
-// One segment per ticket: a wave holding several consecutive segments publishes the later ones'
-// summaries only after writing the earlier ones, so the waves behind it in the same buffer wait for
-// its whole batch (measured: the look-backs run out of polls).  The next ticket is taken while the
-// current segment is processed, which hides the atomic's latency and keeps progress (a wave's
-// prefetched segment is always later than its current one).
-// Since round 3 without the ticket counter: wave w of workgroup k takes segment 4 k + w of a grid
-// of one wave per segment.  A workgroup is dispatched only after every lower-numbered
-// workgroup of its XCD, so the lowest-numbered waiting segment's predecessors are all running or
-// done, and the look-back cannot wait forever (and its polls are bounded regardless: a wave that
-// runs out marks its buffer and exits).
+// SURVEY.md §5's single pass, with the segment held in LDS: a wave loads its segment's <= kResTiles
+// tiles into its LDS region once, summarises them there, publishes the summary, derives its entering
+// state with the decoupled look-back of the fused kernel above, publishes its inclusive state and
+// walks the same LDS tiles again to write.  HBM sees the input once.
+// One segment per wave, and since round 3 without the ticket counter: wave w of workgroup k takes
+// segment 4 k + w of a grid of one wave per segment.  (A wave holding several consecutive segments
+// published the later ones' summaries only after writing the earlier ones, so the waves behind it
+// in the same buffer waited for its whole batch; measured: the look-backs ran out of polls.)  A
+// workgroup is dispatched only after every lower-numbered workgroup of its XCD, so the
+// lowest-numbered waiting segment's predecessors are all running or done, and the look-back cannot
+// wait forever (and its polls are bounded regardless: a wave that runs out marks its buffer and
+// exits).
 __global__ __launch_bounds__(kSegBlock) void enc_seg_res_kernel(const uint8_t* __restrict__ in,
                                                                 const uint64_t* __restrict__ in_off,
                                                                 const uint64_t* __restrict__ in_len,
@@ -433,69 +425,15 @@ __global__ __launch_bounds__(kSegBlock) void enc_seg_res_kernel(const uint8_t* _
     __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];   // enc_tile_fast's selectors
     const u32 lane = threadIdx.x & (kWave - 1);
     const u32 wid = uniform(threadIdx.x / kWave);
-    uint8_t* stage = stage_all + wid * kEncStage;
-    const uint8_t* region = region_all + wid * kResStride;
     for (u32 k = threadIdx.x; k < kInsWaveWords; k += kSegBlock) elut[k] = kEncInsLut.s[k];
     __syncthreads();
+    const EncSingle a{in,   in_off, in_len, out,  out_off, out_len, status, seg_first, maxseg, sb,
+                      summ, incl,   sflag,  lane, region_all + wid * kResStride, stage_all + wid * kEncStage, elut};
     u32 total = uniform(seg_first[n]);
     total = total < maxseg ? total : maxseg;
     (void)ticket;
-    u32 gnext = blockIdx.x * kSegWaves + wid;   // one segment per wave
-    for (;;) {
-        const u32 g = uniform(gnext);
-        if (g >= total) break;
-        gnext = total;
-        {
-            const u32 b = uniform(seg_buf[g]);
-            const u32 s0 = uniform(seg_first[b]), s1 = uniform(seg_first[b + 1]), nseg = s1 - s0;
-            const uint64_t U64 = in_len[b];
-            const uint8_t* src = in + in_off[b];
-            uint8_t* dst = out + out_off[b];
-            u32 bad = (((uintptr_t)src | (uintptr_t)dst) & 15u) ? RLE_STATUS_MISALIGNED : 0u;
-            if (U64 > kMaxBufferBytes || s1 > maxseg) bad |= RLE_STATUS_TOOLARGE;
-            if (bad || U64 == 0u) {   // the buffer's segments all skip (an empty buffer is one segment)
-                if (g == s0 && lane == 0) {
-                    out_len[b] = 0;
-                    if (status) status[b] = bad;
-                }
-                continue;
-            }
-            const u32 U = (u32)U64;
-            u32 p0, p1;
-            seg_range(g - s0, nseg, U, sb, p0, p1);
-            res_load(make_rsrc(src, (U + 15u) & ~15u), p0, ntiles_for(p1 - p0), lane, region);
-            const uint4 sm = enc_seg_summarize<true>(src, U, p0, p1, lane, region);
-            if (lane == 0) publish(summ + g, sm, sflag + g, kFlagAgg);
-            bool late = false;
-            EncCarry c{0u, 0u};
-            u32 lateb = 0u;
-            if (g > s0) {
-                const u32 from = seg_lookback(g, s0, sflag, lane, late);
-                if (from > s0) {
-                    const uint4 in4 = ld_relaxed4(incl + (from - 1u));
-                    c = EncCarry{uniform(in4.x), uniform(in4.y)};
-                    lateb = uniform(in4.z);
-                }
-                for (u32 base = from; base < g; base += kWave) {
-                    const u32 j = base + lane;
-                    const bool valid = j < g;
-                    const uint4 smj = valid ? ld_relaxed4(summ + j) : make_uint4(0u, 0u, 0u, 0u);
-                    enc_seg_window(smj, valid, (j - s0) * sb, c);
-                }
-            }
-            const uint2 mine = enc_seg_window(sm, lane == 0u, p0, c);
-            lateb |= late ? RLE_STATUS_INTERNAL : 0u;
-            if (lane == 0) {
-                publish(incl + g, make_uint4(c.lb1, c.off, lateb, 0u), sflag + g, kFlagIncl);
-                if (late && status) atomicOr(status + b, RLE_STATUS_INTERNAL);   // (as enc_seg_fused_kernel)
-                if (g + 1u == s1) {   // the buffer's last segment: C and the status
-                    out_len[b] = c.off;
-                    if (lateb && status) atomicOr(status + b, lateb);
-                }
-            }
-            enc_seg_write<true>(src, dst, U, p0, p1, uniform(mine.x), uniform(mine.y), lane, region, stage, elut);
-        }
-    }
+    const u32 g = blockIdx.x * kSegWaves + wid;   // one segment per wave
+    if (g < total) enc_seg_single<true>(a, g, uniform(seg_buf[g]));
 }
 #endif  // RLE_VARIANTS
 
@@ -709,21 +647,17 @@ __global__ __launch_bounds__(kSegBlock) void dec_seg_summary_kernel(const uint8_
     for (u32 k = threadIdx.x; k < 256u; k += kSegBlock) tbl[k] = dec_entry_from(kDecTable.e[k]);
     __syncthreads();
     const uint8_t* slots = slots_all + wid * 2 * kSlot;
-    u32 total = seg_total(seg_first, n, in_len, sb);
-    total = total < maxseg ? total : maxseg;
-    for (u32 g = blockIdx.x * kSegWaves + wid; g < total; g += gridDim.x * kSegWaves) {
-        const u32 b = seg_of(seg_buf, g);
-        const u32 s0 = seg_lo(seg_first, b), nseg = seg_hi(seg_first, b, in_len, sb) - s0;
-        const uint64_t C64 = in_len[b];
-        const uint8_t* src = in + in_off[b];
+    seg_walk<false>(SegCut{seg_first, seg_buf, in_len, n, maxseg, sb}, wid, SegScanned{}, [&](const Seg& s) {
+        const uint64_t C64 = in_len[s.b];
+        const uint8_t* src = in + in_off[s.b];
         uint4 res = kDecEmpty;
         if (C64 > 0 && C64 <= kMaxBufferBytes && !((uintptr_t)src & 15u)) {
             u32 q0, q1;
-            seg_range(g - s0, nseg, (u32)C64, sb, q0, q1);
+            seg_range(s.g - s.s0, s.nseg, (u32)C64, sb, q0, q1);
             res = dec_seg_summarize(src, (u32)C64, q0, q1, lane, slots, tbl);
         }
-        if (lane == 0) summ[g] = res;
-    }
+        if (lane == 0) summ[s.g] = res;
+    });
 }
 
 // The carried state of a decode scan over a buffer's segments: the entry phase, the output offset
@@ -858,26 +792,21 @@ __global__ __launch_bounds__(kSegBlock) void dec_seg_write_kernel(const uint8_t*
     for (u32 k = lane; k < kStage / 16u; k += kWave)
         reinterpret_cast<u32x4*>(stage)[k] = u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
-    u32 total = seg_total(seg_first, n, in_len, sb);
-    total = total < maxseg ? total : maxseg;
-    for (u32 g0 = blockIdx.x * kSegWaves + wid; g0 < total; g0 += gridDim.x * kSegWaves) {
-        const u32 g = total - 1u - g0;
-        const uint2 pl = plan[g];
-        const uint4 sm = summ[g];
-        const u32 b = seg_of(seg_buf, g);
-        const u32 flag = uniform(bflag[b]);
-        if (flag & kFlagSkip) continue;
-        const u32 s0 = seg_lo(seg_first, b), nseg = seg_hi(seg_first, b, in_len, sb) - s0;
+    const SegScanned scanned{plan, bflag, summ};
+    seg_walk<true>(SegCut{seg_first, seg_buf, in_len, n, maxseg, sb}, wid, scanned, [&](const Seg& s) {
+        const u32 g = s.g, b = s.b, s0 = s.s0, nseg = s.nseg;
+        const uint2 pl = s.pl;
+        const uint4 sm = s.sm;
         const u32 C = (u32)in_len[b], U = (u32)out_len[b];
         const uint8_t* src = in + in_off[b];
         uint8_t* dst = out + out_off[b];
-        if (flag & kFlagSerial) {   // one wave decodes the whole buffer exactly
+        if (s.flag & kFlagSerial) {   // one wave decodes the whole buffer exactly
             if (g == s0) {
                 const uint64_t cap = out_cap ? out_cap[b] : (uint64_t)U;
                 const u32 stat = dec_serial(src, C, U, cap, dst, lane, stage, kStage);
                 if (lane == 0 && status) status[b] = stat;
             }
-            continue;
+            return;
         }
         u32 q0, q1;
         seg_range(g - s0, nseg, C, sb, q0, q1);
@@ -886,12 +815,12 @@ __global__ __launch_bounds__(kSegBlock) void dec_seg_write_kernel(const uint8_t*
             if ((uniform(sm.w) >> (11u + e)) & 1u) {
                 const u32 cnt = uniform(e == 0u ? sm.x : (e == 1u ? sm.y : sm.z));
                 dec_seg_fill(dst, U, uniform(pl.y), cnt, src[q0 + e], lane);
-                continue;
+                return;
             }
         }
         dec_seg_write<false, kSegDecChunks>(src, dst, C, U, q0, q1, uniform(pl.x), uniform(pl.y), g + 1u == s0 + nseg,
                                             lane, slots, stage, tbl, clut, status ? status + b : nullptr);
-    }
+    });
 }
 
 
@@ -1040,39 +969,6 @@ CuCache& cu_cache() {
     static CuCache* p = new CuCache();   // never destroyed: launches may run during exit
     return *p;
 }
-// 256 B-aligned carve-up of the workspace
-struct Carve {
-    uint32_t* seg_first;
-    uint32_t* seg_buf;   // per-segment buffer index (seg_map_kernel)
-    uint4* summ;
-    uint2* plan;
-    uint32_t* bflag;
-    uint32_t* sflag;    // fused kernels: per-segment publication flag
-    uint4* incl;        // fused kernels: per-segment inclusive state
-    uint32_t* ticket;   // fused kernels: segment ticket counter
-    size_t bytes;
-};
-inline size_t al(size_t x) { return (x + 255u) & ~(size_t)255u; }
-Carve carve(char* base, uint32_t n, uint32_t maxseg) {
-    Carve c;
-    size_t o = 0;
-    c.seg_first = reinterpret_cast<uint32_t*>(base + o); o += al(sizeof(uint32_t) * ((size_t)n + 1));
-    c.seg_buf = reinterpret_cast<uint32_t*>(base + o);   o += al(sizeof(uint32_t) * (size_t)maxseg);
-    c.summ = reinterpret_cast<uint4*>(base + o);         o += al(sizeof(uint4) * (size_t)maxseg);
-    c.plan = reinterpret_cast<uint2*>(base + o);         o += al(sizeof(uint2) * (size_t)maxseg);
-    c.bflag = reinterpret_cast<uint32_t*>(base + o);     o += al(sizeof(uint32_t) * (size_t)n);
-    c.sflag = reinterpret_cast<uint32_t*>(base + o);     o += al(sizeof(uint32_t) * (size_t)maxseg);
-    c.incl = reinterpret_cast<uint4*>(base + o);         o += al(sizeof(uint4) * (size_t)maxseg);
-    c.ticket = reinterpret_cast<uint32_t*>(base + o);    o += al(sizeof(uint32_t));
-    c.bytes = o;
-    return c;
-}
-// upper bound on the segments of n buffers holding total bytes (each segment but a buffer's
-// last covers sb bytes)
-inline uint32_t max_segments(uint32_t n, uint64_t total, uint32_t sb) {
-    const uint64_t m = total / (sb - 2u) + n;
-    return m > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)m;
-}
 int device_cus(int* ncu) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return RLE_E_HIP;
@@ -1087,25 +983,42 @@ int device_cus(int* ncu) {
     *ncu = c->second;
     return RLE_OK;
 }
-// segment length in bytes: about 16 segments per CU over the batch, 4..16 tiles each
-// (longer segments, caps of 32 / 64 tiles, measured slower on the mixed batch: r5w, DESIGN.md §4)
-// The resident single-pass kernels (enc_seg_res_kernel / dec_seg_res_kernel): RLE_MI355X_SEG_RES=1|0
-// overrides the build default.  Their segments are one tile shorter than an LDS region, so that a
-// buffer's last segment (which absorbs a remainder of up to 2 bytes) still fits.  Segment lengths
-// stay whole tiles: a segment's exit state is read after the last tile's last lane (an 8048-byte
-// segment, measured, left the decode exit phase one lane late).
-// 0 off, 1 the resident single pass, 2 the single pass without the resident segment (decode)
+inline size_t al(size_t x) { return (x + 255u) & ~(size_t)255u; }
+// upper bound on the segments of n buffers holding total bytes (each segment but a buffer's
+// last covers sb bytes)
+inline uint32_t max_segments(uint32_t n, uint64_t total, uint32_t sb) {
+    const uint64_t m = total / (sb - 2u) + n;
+    return m > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)m;
+}
+#if RLE_VARIANTS   // (the product build reads neither variable)
+// RLE_MI355X_SEG_RES: 0 off, 1 the resident single pass (enc_seg_res_kernel / dec_seg_res_kernel),
+// 2 the single pass without the resident segment (decode)
 int seg_res_mode() {
-    if (!RLE_VARIANTS) return 0;   // (product build: RLE_MI355X_SEG_RES is not read)
     static const int m = [] {
         const char* e = getenv("RLE_MI355X_SEG_RES");
         return e ? atoi(e) : 0;
     }();
     return m;
 }
-bool seg_res() { return seg_res_mode() == 1; }
+// the fused single-pass encode (RLE_MI355X_SEG_FUSED=1; measured slower than the four launches, §4)
+bool seg_fused() {
+    static const bool on = [] {
+        const char* e = getenv("RLE_MI355X_SEG_FUSED");
+        return e ? e[0] != '0' : false;
+    }();
+    return on;
+}
+#endif
+// segment length in bytes: about 16 segments per CU over the batch, 4..16 tiles each
+// (longer segments, caps of 32 / 64 tiles, measured slower on the mixed batch: r5w, DESIGN.md §4)
+// The resident kernels' segments are one tile shorter than an LDS region, so that a buffer's last
+// segment (which absorbs a remainder of up to 2 bytes) still fits.  Segment lengths stay whole
+// tiles: a segment's exit state is read after the last tile's last lane (an 8048-byte segment,
+// measured, left the decode exit phase one lane late).
 inline uint32_t seg_bytes(uint64_t total, int ncu) {
-    if (seg_res()) return (rle::kResTiles - 1u) * rle::kTileStep;
+#if RLE_VARIANTS
+    if (seg_res_mode() == 1) return (rle::kResTiles - 1u) * rle::kTileStep;
+#endif
     const uint64_t tiles = (total + rle::kTileStep - 1) / rle::kTileStep;
     uint64_t per = tiles / ((uint64_t)ncu * 16u);
     per = per < rle::kSegTilesMin ? rle::kSegTilesMin : (per > rle::kSegTilesMax ? rle::kSegTilesMax : per);
@@ -1122,50 +1035,66 @@ inline uint32_t seg_grid(uint32_t maxseg, int ncu) {
     const uint32_t g = need < fill ? need : fill;
     return g ? g : 1u;
 }
-inline uint32_t map_grid(uint32_t maxseg) { return (maxseg + rle::kMapBlock - 1) / rle::kMapBlock; }
-inline uint32_t buf_grid(uint32_t n) { return (n + rle::kSegWaves - 1) / rle::kSegWaves; }
-// the fused single-pass encode (RLE_MI355X_SEG_FUSED=1; measured slower than the four launches, §4)
-[[maybe_unused]] bool seg_fused() {
-    if (!RLE_VARIANTS) return false;   // (product build: RLE_MI355X_SEG_FUSED is not read)
-    static const bool on = [] {
-        const char* e = getenv("RLE_MI355X_SEG_FUSED");
-        return e ? e[0] != '0' : false;
-    }();
-    return on;
+// The launch shape: segment length, segment bound, grid, and the carve-up of the workspace at base
+// (the three single-pass tables are carved in every build: the size is part of the contract).
+rle::SegShape seg_shape(char* base, uint32_t n, uint64_t total, int ncu, size_t extra) {
+    rle::SegShape sh;
+    sh.ncu = ncu;
+    sh.sb = seg_bytes(total, ncu);
+    sh.maxseg = max_segments(n, total, sh.sb);
+    sh.grid = seg_grid(sh.maxseg, ncu);
+    const size_t m = sh.maxseg;
+    size_t o = 0;
+    const auto take = [&](size_t bytes) {
+        char* const p = base ? base + o : nullptr;
+        o += al(bytes);
+        return p;
+    };
+    sh.seg_first = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * ((size_t)n + 1)));
+    sh.seg_buf = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * m));
+    sh.summ = reinterpret_cast<uint4*>(take(sizeof(uint4) * m));
+    sh.plan = reinterpret_cast<uint2*>(take(sizeof(uint2) * m));
+    sh.bflag = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * (size_t)n));
+    sh.sflag = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * m));
+    sh.incl = reinterpret_cast<uint4*>(take(sizeof(uint4) * m));
+    sh.ticket = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t)));
+    sh.extra = take(extra);
+    sh.bytes = o;
+    return sh;
 }
 }  // namespace
 
-// The launch shape for other translation units (rle_seg_device.h): the same segment length, segment
-// bound, grid and carve-up as the entry points below.
 namespace rle {
-int seg_device_cus(int* ncu) { return device_cus(ncu); }
-SegShape seg_shape(char* base, uint32_t n, uint64_t total, int ncu) {
-    if (ncu <= 0) ncu = 256;
-    const uint32_t sb = seg_bytes(total, ncu);
-    const uint32_t maxseg = max_segments(n, total, sb);
-    const Carve w = carve(base, n, maxseg);
-    return SegShape{sb, maxseg, seg_grid(maxseg, ncu), w.seg_first, w.seg_buf, w.summ, w.plan, w.bflag, w.bytes};
+int seg_prologue(void* d_workspace, size_t workspace_bytes, uint32_t n, uint64_t total, size_t extra, SegShape* sh) {
+    int ncu = 0;
+    const int have = device_cus(&ncu);
+    *sh = seg_shape(static_cast<char*>(d_workspace), n, total, have == RLE_OK ? ncu : 256, extra);
+    if (!d_workspace || workspace_bytes < sh->bytes) return RLE_E_INVAL;
+    if (have != RLE_OK) return have;
+    if (n == 1u) sh->seg_first = sh->seg_buf = nullptr;
+    return RLE_OK;
 }
-void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hipStream_t s) {
-    hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(1024), 0, s, len, n, sh.sb, sh.seg_first, nullptr, 0u, nullptr,
-                       nullptr);
-    hipLaunchKernelGGL(seg_map_kernel, dim3(map_grid(sh.maxseg)), dim3(kMapBlock), 0, s, sh.seg_first, n, sh.maxseg,
-                       sh.seg_buf);
+void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hipStream_t s, uint32_t* sflag,
+                         uint32_t* ticket, uint32_t* bclear) {
+    if (!sh.seg_first) return;
+    hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(1024), 0, s, len, n, sh.sb, sh.seg_first, sflag, sh.maxseg, ticket,
+                       bclear);
+    hipLaunchKernelGGL(seg_map_kernel, dim3((sh.maxseg + kMapBlock - 1) / kMapBlock), dim3(kMapBlock), 0, s,
+                       sh.seg_first, n, sh.maxseg, sh.seg_buf);
 }
 }  // namespace rle
 
 extern "C" size_t rle_seg_workspace_bytes(uint32_t n, uint64_t total_in_bytes) {
-    int ncu = 0;
-    if (device_cus(&ncu) != RLE_OK) ncu = 256;
-    const uint32_t sb = seg_bytes(total_in_bytes, ncu);
-    return carve(nullptr, n, max_segments(n, total_in_bytes, sb)).bytes;
+    rle::SegShape sh;
+    rle::seg_prologue(nullptr, 0, n, total_in_bytes, 0, &sh);
+    return sh.bytes;
 }
 
 // host only: the segment length a launch with this total_in_bytes takes (tests name it)
 extern "C" uint32_t rle_seg_segment_bytes(uint64_t total_in_bytes) {
-    int ncu = 0;
-    if (device_cus(&ncu) != RLE_OK) ncu = 256;
-    return seg_bytes(total_in_bytes, ncu);
+    rle::SegShape sh;
+    rle::seg_prologue(nullptr, 0, 1, total_in_bytes, 0, &sh);
+    return sh.sb;
 }
 
 extern "C" int rle_encode_batch_device_seg(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -1174,53 +1103,39 @@ extern "C" int rle_encode_batch_device_seg(const void* d_in, const uint64_t* d_i
                                            size_t workspace_bytes, void* stream) {
     if (n == 0) return RLE_OK;
     if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len) return RLE_E_INVAL;
+    rle::SegShape sh;
+    if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_in_bytes, 0, &sh)) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    int ncu = 0;
-    if (const int rc = device_cus(&ncu)) return rc;
-    const uint32_t sb = seg_bytes(total_in_bytes, ncu);
-    const uint32_t maxseg = max_segments(n, total_in_bytes, sb);
-    const Carve w = carve(static_cast<char*>(d_workspace), n, maxseg);
-    if (!d_workspace || workspace_bytes < w.bytes) return RLE_E_INVAL;
     const uint8_t* in = (const uint8_t*)d_in;
     uint8_t* out = (uint8_t*)d_out;
 #if RLE_VARIANTS
-    if (seg_res()) {   // (the plan clears the status words: the segments OR into them)
-        hipLaunchKernelGGL(rle::seg_plan_kernel, dim3(1), dim3(1024), 0, s, d_in_len, n, sb, w.seg_first, w.sflag,
-                           maxseg, w.ticket, d_status);
-        hipLaunchKernelGGL(rle::seg_map_kernel, dim3(map_grid(maxseg)), dim3(rle::kMapBlock), 0, s, w.seg_first, n,
-                           maxseg, w.seg_buf);
-        hipLaunchKernelGGL(rle::enc_seg_res_kernel, dim3(buf_grid(maxseg)),
-                           dim3(rle::kSegBlock), 0, s, in,
-                           d_in_off, d_in_len, out, d_out_off, d_out_len, d_status, n, w.seg_first, w.seg_buf, maxseg,
-                           sb, w.summ, w.incl, w.sflag, w.ticket);
+    // (the single-pass kernels take the tables for one buffer too; their plan clears the status
+    // words: the segments OR into them)
+    if (seg_res_mode() == 1 || seg_fused()) sh = seg_shape(static_cast<char*>(d_workspace), n, total_in_bytes, sh.ncu, 0);
+    if (seg_res_mode() == 1) {
+        rle::seg_launch_plan_map(d_in_len, n, sh, s, sh.sflag, sh.ticket, d_status);
+        hipLaunchKernelGGL(rle::enc_seg_res_kernel, dim3(rle::seg_buf_grid(sh.maxseg)), dim3(rle::kSegBlock), 0, s, in,
+                           d_in_off, d_in_len, out, d_out_off, d_out_len, d_status, n, sh.seg_first, sh.seg_buf,
+                           sh.maxseg, sh.sb, sh.summ, sh.incl, sh.sflag, sh.ticket);
         return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
     }
-    if (seg_fused()) {   // (the plan clears the status words: the segments OR into them)
-        hipLaunchKernelGGL(rle::seg_plan_kernel, dim3(1), dim3(1024), 0, s, d_in_len, n, sb, w.seg_first, w.sflag,
-                           maxseg, w.ticket, d_status);
-        hipLaunchKernelGGL(rle::enc_seg_fused_kernel, dim3(seg_grid(maxseg, ncu)), dim3(rle::kSegBlock), 0, s, in,
-                           d_in_off, d_in_len, out, d_out_off, d_out_len, d_status, n, w.seg_first, maxseg, sb, w.summ,
-                           w.incl, w.sflag, w.ticket);
+    if (seg_fused()) {   // (finds a segment's buffer by binary search: the plan alone, no map)
+        hipLaunchKernelGGL(rle::seg_plan_kernel, dim3(1), dim3(1024), 0, s, d_in_len, n, sh.sb, sh.seg_first, sh.sflag,
+                           sh.maxseg, sh.ticket, d_status);
+        hipLaunchKernelGGL(rle::enc_seg_fused_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len,
+                           out, d_out_off, d_out_len, d_status, n, sh.seg_first, sh.maxseg, sh.sb, sh.summ, sh.incl,
+                           sh.sflag, sh.ticket);
         return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
     }
 #endif
-    const uint32_t grid = seg_grid(maxseg, ncu);
-    // one buffer: no plan / map launches, the kernels take its segments from its length
-    const bool one = n == 1u;
-    uint32_t* const seg_first = one ? nullptr : w.seg_first;
-    uint32_t* const seg_buf = one ? nullptr : w.seg_buf;
-    if (!one) {
-        hipLaunchKernelGGL(rle::seg_plan_kernel, dim3(1), dim3(1024), 0, s, d_in_len, n, sb, w.seg_first, nullptr, 0u,
-                           nullptr, nullptr);
-        hipLaunchKernelGGL(rle::seg_map_kernel, dim3(map_grid(maxseg)), dim3(rle::kMapBlock), 0, s, w.seg_first, n,
-                           maxseg, w.seg_buf);
-    }
-    hipLaunchKernelGGL(rle::enc_seg_summary_kernel, dim3(grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len, n,
-                       seg_first, seg_buf, maxseg, sb, w.summ);
-    hipLaunchKernelGGL(rle::enc_seg_scan_kernel, dim3(buf_grid(n)), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len,
-                       out, d_out_off, d_out_len, d_status, n, seg_first, maxseg, sb, w.summ, w.plan, w.bflag);
-    hipLaunchKernelGGL(rle::enc_seg_write_kernel, dim3(grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len, out,
-                       d_out_off, n, seg_first, seg_buf, maxseg, sb, w.plan, w.bflag, w.summ);
+    rle::seg_launch_plan_map(d_in_len, n, sh, s);
+    hipLaunchKernelGGL(rle::enc_seg_summary_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len,
+                       n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, sh.summ);
+    hipLaunchKernelGGL(rle::enc_seg_scan_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, in, d_in_off,
+                       d_in_len, out, d_out_off, d_out_len, d_status, n, sh.seg_first, sh.maxseg, sh.sb, sh.summ,
+                       sh.plan, sh.bflag);
+    hipLaunchKernelGGL(rle::enc_seg_write_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len,
+                       out, d_out_off, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, sh.plan, sh.bflag, sh.summ);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }
 
@@ -1231,49 +1146,34 @@ extern "C" int rle_decode_batch_device_seg(const void* d_in, const uint64_t* d_i
                                            void* stream) {
     if (n == 0) return RLE_OK;
     if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len) return RLE_E_INVAL;
+    rle::SegShape sh;
+    if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_in_bytes, 0, &sh)) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    int ncu = 0;
-    if (const int rc = device_cus(&ncu)) return rc;
-    const uint32_t sb = seg_bytes(total_in_bytes, ncu);
-    const uint32_t maxseg = max_segments(n, total_in_bytes, sb);
-    const Carve w = carve(static_cast<char*>(d_workspace), n, maxseg);
-    if (!d_workspace || workspace_bytes < w.bytes) return RLE_E_INVAL;
     const uint8_t* in = (const uint8_t*)d_in;
     uint8_t* out = (uint8_t*)d_out;
 #if RLE_VARIANTS
-    if (seg_res_mode() == 1 || seg_res_mode() == 2) {
-        hipLaunchKernelGGL(rle::seg_plan_kernel, dim3(1), dim3(1024), 0, s, d_in_len, n, sb, w.seg_first, w.sflag,
-                           maxseg, w.ticket, w.bflag);
-        hipLaunchKernelGGL(rle::seg_map_kernel, dim3(map_grid(maxseg)), dim3(rle::kMapBlock), 0, s, w.seg_first, n,
-                           maxseg, w.seg_buf);
+    if (seg_res_mode() == 1 || seg_res_mode() == 2) {   // (the tables for one buffer too)
+        sh = seg_shape(static_cast<char*>(d_workspace), n, total_in_bytes, sh.ncu, 0);
+        rle::seg_launch_plan_map(d_in_len, n, sh, s, sh.sflag, sh.ticket, sh.bflag);
         hipLaunchKernelGGL(seg_res_mode() == 1 ? rle::dec_seg_res_kernel<true> : rle::dec_seg_res_kernel<false>,
-                           dim3(buf_grid(maxseg)),
-                           dim3(rle::kSegBlock), 0, s, in,
-                           d_in_off, d_in_len, out, d_out_off, d_out_len, d_out_cap, d_status, n, w.seg_first,
-                           w.seg_buf, maxseg, sb, w.summ, w.incl, w.sflag, w.ticket, w.bflag);
-        hipLaunchKernelGGL(rle::dec_seg_serial_kernel, dim3(buf_grid(n)), dim3(rle::kSegBlock), 0, s, in, d_in_off,
-                           d_in_len, out, d_out_off, d_out_len, d_out_cap, d_status, n, w.bflag);
+                           dim3(rle::seg_buf_grid(sh.maxseg)), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len, out,
+                           d_out_off, d_out_len, d_out_cap, d_status, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb,
+                           sh.summ, sh.incl, sh.sflag, sh.ticket, sh.bflag);
+        hipLaunchKernelGGL(rle::dec_seg_serial_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, in,
+                           d_in_off, d_in_len, out, d_out_off, d_out_len, d_out_cap, d_status, n, sh.bflag);
         return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
     }
 #endif
-    const uint32_t grid = seg_grid(maxseg, ncu);
-    const bool one = n == 1u;   // (as in the encode: no plan / map launches for one buffer)
-    uint32_t* const seg_first = one ? nullptr : w.seg_first;
-    uint32_t* const seg_buf = one ? nullptr : w.seg_buf;
-    if (!one) {
-        hipLaunchKernelGGL(rle::seg_plan_kernel, dim3(1), dim3(1024), 0, s, d_in_len, n, sb, w.seg_first, nullptr, 0u,
-                           nullptr, nullptr);
-        hipLaunchKernelGGL(rle::seg_map_kernel, dim3(map_grid(maxseg)), dim3(rle::kMapBlock), 0, s, w.seg_first, n,
-                           maxseg, w.seg_buf);
-    }
-    hipLaunchKernelGGL(rle::dec_seg_summary_kernel, dim3(grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len, n,
-                       seg_first, seg_buf, maxseg, sb, w.summ);
-    hipLaunchKernelGGL(rle::dec_seg_scan_kernel, dim3(buf_grid(n)), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len,
-                       out, d_out_off, d_out_len, d_out_cap, d_status, n, seg_first, maxseg, sb, w.summ, w.plan, w.bflag);
-    const bool one_round = maxseg <= (uint32_t)ncu * 16u;   // the 192-chunk kernel's residency
+    rle::seg_launch_plan_map(d_in_len, n, sh, s);
+    hipLaunchKernelGGL(rle::dec_seg_summary_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len,
+                       n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, sh.summ);
+    hipLaunchKernelGGL(rle::dec_seg_scan_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, in, d_in_off,
+                       d_in_len, out, d_out_off, d_out_len, d_out_cap, d_status, n, sh.seg_first, sh.maxseg, sh.sb,
+                       sh.summ, sh.plan, sh.bflag);
+    const bool one_round = sh.maxseg <= (uint32_t)sh.ncu * 16u;   // the 192-chunk kernel's residency
     hipLaunchKernelGGL(one_round ? rle::dec_seg_write_kernel<rle::kSegDecChunksOne>
                                  : rle::dec_seg_write_kernel<rle::kSegDecChunksMany>,
-                       dim3(grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len, out, d_out_off, d_out_len,
-                       d_out_cap, d_status, n, seg_first, seg_buf, maxseg, sb, w.plan, w.bflag, w.summ);
+                       dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len, out, d_out_off, d_out_len,
+                       d_out_cap, d_status, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, sh.plan, sh.bflag, sh.summ);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }

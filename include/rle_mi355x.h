@@ -145,6 +145,8 @@ int rle_mi355x_selftest(void);
  *                   segments do not fit gets RLE_STATUS_TOOLARGE)
  *   d_workspace     caller-owned device memory of at least rle_seg_workspace_bytes(n,
  *                   total_in_bytes) bytes, 256-byte aligned, not used by another launch in flight
+ * Decided on the host before anything is launched: n == 0 is RLE_OK; a NULL d_in, d_in_off, d_in_len,
+ * d_out, d_out_off, d_out_len or d_workspace, or workspace_bytes below that size, is RLE_E_INVAL.
  * Use it when buffers are large relative to the batch (one big file, a mixed 4 KiB - 1 MiB batch);
  * RLEcompress / RLEdecompress use it from 48 KiB (encode input) / 32 KiB (decode input).
  * Replaces src/rleCompression.c:9-62 like the entries above. */
