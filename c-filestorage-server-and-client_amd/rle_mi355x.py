@@ -326,7 +326,9 @@ def _ws_ptr(ws):
 
 def encode_batch_seg(d_in, in_off, in_len, d_out, out_off, out_len, status=None, total_in_bytes=None,
                      workspace=None, stream=None):
-    """Segmented batched encode (several waves per buffer; for large buffers)."""
+    """Segmented batched encode (several waves per buffer; for large buffers).  The default
+    total_in_bytes (the sum of in_len, read back from the device) synchronises, and the default
+    workspace is allocated here: a call captured into a graph must pass both."""
     n = in_off.numel()
     total = int(in_len.sum().item()) if total_in_bytes is None else int(total_in_bytes)
     ws = workspace if workspace is not None else seg_workspace(n, total, d_in.device)
@@ -339,7 +341,9 @@ def encode_batch_seg(d_in, in_off, in_len, d_out, out_off, out_len, status=None,
 
 def decode_batch_seg(d_in, in_off, in_len, d_out, out_off, out_len, out_cap=None, status=None,
                      total_in_bytes=None, workspace=None, stream=None):
-    """Segmented batched decode (several waves per buffer; for large buffers)."""
+    """Segmented batched decode (several waves per buffer; for large buffers).  The default
+    total_in_bytes (the sum of in_len, read back from the device) synchronises, and the default
+    workspace is allocated here: a call captured into a graph must pass both."""
     n = in_off.numel()
     total = int(in_len.sum().item()) if total_in_bytes is None else int(total_in_bytes)
     ws = workspace if workspace is not None else seg_workspace(n, total, d_in.device)
@@ -427,7 +431,9 @@ def append_batch_seg(d_streams, off, length, cap, ulen, d_new, new_off, new_len,
     """rle_append_batch_device_seg: append_batch with several waves per file, for new content that is
     large next to the batch.  total_new_bytes (>= the sum of new_len; default: that sum) sizes the
     segment tables; workspace: from append_seg_workspace (default: a fresh one).  Returns the tail
-    tensor, as append_batch does."""
+    tensor, as append_batch does.  The default total_new_bytes synchronises (the sum is read back
+    from the device) and the default tail launches a scan into a new tensor: a call captured into a
+    graph must pass total_new_bytes, workspace and tail."""
     n = off.numel()
     if tail is None:
         import torch

@@ -23,6 +23,20 @@
  *    written); the first U bytes are always written.  Bytes of a slot past U are written only for streams
  *    the encoder never emits and only where the reference would write them (its
  *    extraAllocation region).
+ *
+ * Graph capture (tests/test_gpu_graph_replay.py): the batch entry points -- rle_encode_batch_device,
+ * rle_decode_batch_device, their *_sized and *_sized_flags forms, the *_seg forms,
+ * rle_append_batch_device, rle_append_batch_device_seg and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
+ * (global) capture mode, and the graph replayed any number of times.  The host freezes at capture
+ * what it decides itself: the kernel form (from n, the max_* hints and the cooperative mode), the
+ * grid, the segment length and table sizes (from the total_* hint), every pointer including the
+ * workspace, and rle_append_prepare_device's U.  Everything else is read from device memory on each
+ * replay: offsets, lengths, capacities, tail words and the data may all be rewritten between replays,
+ * within the hints given at capture; every status word, length and table is written again by each
+ * replay.  The caller keeps every buffer it passed, the workspace included, alive and out of other
+ * launches' hands while the graph exists.  A decode of more than 4096 buffers does not use the
+ * stream's cached issue-order array under capture: the graph holds its own allocation and release of
+ * the array (stream-ordered memory nodes) around the sort and decode kernels.
  */
 #ifndef RLE_MI355X_H
 #define RLE_MI355X_H
