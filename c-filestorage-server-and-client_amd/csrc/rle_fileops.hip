@@ -11,7 +11,9 @@
 // The second half of the file is the same append on streams that stay in device memory, without
 // decoding them: the tail scan and the append in place (rle_tail_batch_device,
 // rle_append_batch_device), and the append's segmented form for large new content
-// (rle_append_batch_device_seg: several waves per file, on the segmented encode's device code).
+// (rle_append_batch_device_seg: several waves per file, on the segmented encode's device code) and
+// the scan's segmented form for large stored streams (rle_tail_batch_device_seg: the segmented
+// decode's summaries and a per-stream scan of its own).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -119,6 +121,29 @@ __host__ __device__ inline uint64_t append_slot_bytes(uint64_t C, uint64_t A) {
     return s > RLE_MAX_BUFFER_BYTES ? 0u : s;
 }
 
+// The last token start of the tile at pos (S80: 0x80 per start among the owned positions), into
+// `last` when the tile has one.
+__device__ __forceinline__ void tail_tile_last(const DecLen& ln, u32 pos, const DecK& kc, u32& last) {
+    constexpr uint64_t kOwned = (1ull << kOwnLanes) - 1ull;
+    const u32 sa = __builtin_amdgcn_udot4(ln.S80[1], kc.C2, __builtin_amdgcn_udot4(ln.S80[0], kc.C1, 0u, false), false);
+    const u32 sb = __builtin_amdgcn_udot4(ln.S80[3], kc.C2, __builtin_amdgcn_udot4(ln.S80[2], kc.C1, 0u, false), false);
+    const u32 S16 = ((sa >> 7) | (sb << 1)) & 0xFFFFu;
+    const uint64_t has = __builtin_amdgcn_ballot_w64(S16 != 0u) & kOwned;
+    if (has) {
+        const u32 hl = 63u - (u32)__builtin_clzll(has);
+        last = pos + 16u * hl + 31u - (u32)__builtin_clz(readlane(S16, hl));
+    }
+}
+// tail_scan_kernel's closing rule for the segmented scan: the parse of a C-byte stream (C > 0) ends
+// at C exactly when its final token, starting at `last`, is y[C-1] alone or "v v digit" with a digit
+// 1..9.  The tail word, or 0 (RLE_STATUS_NOTCANON).
+__device__ __forceinline__ uint64_t tail_close(const uint8_t* src, u32 C, u32 last) {
+    u32 r = 1u;
+    if (last + 1u != C) r = uniform((u32)src[C - 1u]) - 0x30u;
+    if ((last + 1u != C && last + 3u != C) || r < 1u || r > 9u) return 0u;
+    return (uint64_t)last | ((uint64_t)r << 32);
+}
+
 // One wave per stream: the decode's tiles (LDS-DMA, dec_prepare, dec_lengths) without its scatter,
 // staging and stores.  Per tile: the count-digit validation (a 3-byte token whose digit is not
 // '2'..'9', or lies past C while its second byte does not, stops the walk), the decoded length of the
@@ -158,15 +183,7 @@ __global__ __launch_bounds__(kFileBlock) void tail_scan_kernel(const uint8_t* __
             const DecLen ln = dec_lengths(pr, d);
             if (__builtin_amdgcn_ballot_w64(ln.serial_lane) & kOwned) return ~0u;
             U += readlane(wave_scan_incl(ln.nout, 0u, OpAdd()), kOwnLanes - 1u);
-            // the tile's last token start (S80: 0x80 per start among the owned positions)
-            const u32 sa = __builtin_amdgcn_udot4(ln.S80[1], kc.C2, __builtin_amdgcn_udot4(ln.S80[0], kc.C1, 0u, false), false);
-            const u32 sb = __builtin_amdgcn_udot4(ln.S80[3], kc.C2, __builtin_amdgcn_udot4(ln.S80[2], kc.C1, 0u, false), false);
-            const u32 S16 = ((sa >> 7) | (sb << 1)) & 0xFFFFu;
-            const uint64_t has = __builtin_amdgcn_ballot_w64(S16 != 0u) & kOwned;
-            if (has) {
-                const u32 hl = 63u - (u32)__builtin_clzll(has);
-                last = pos + 16u * hl + 31u - (u32)__builtin_clz(readlane(S16, hl));
-            }
+            tail_tile_last(ln, pos, kc, last);
             d = bfe(readlane(pr.incl, kOwnLanes - 1u), 8u * d, 8);
             return 0u;
         });
@@ -456,6 +473,92 @@ __global__ __launch_bounds__(kSegBlock) void append_seg_write_kernel(uint8_t* st
                        stage_all, elut, [=](u32 b) { return app_view(entry, streams, off, newb, new_off, new_len, b); });
 }
 
+// ================================================================ segmented tail scan
+// rle_tail_batch_device_seg: the tail scan with several waves per stream (one wave walks the 1041
+// dependent tiles of a 1 MiB stream while the chip idles).  The stream is cut into the segmented
+// decode's segments and summarised by its summary launch itself (seg_launch_dec_summary: per segment
+// and entry phase 0..2 the decoded bytes, the exit phase and whether the parse stops: dec_lengths'
+// serial_lane on an owned lane, tail_scan_kernel's test).  The scan below, one wave per stream, makes
+// the per-stream checks, composes the phase maps over windows of 64 segments, sums the counts of the
+// phases taken (64 bits across windows: U is the result here and may pass 4 GiB) and refuses the
+// stream when a taken phase stops.  The cut puts the final token's start into the last segment (it
+// absorbs a remainder of 1-2 bytes), so the same wave then walks that one segment, at most 17 tiles,
+// from its now known entry phase with tail_scan_kernel's tile body for the last token start, and
+// closes as the one-wave scan does.  Nothing is recorded per stream, so the workspace is the
+// decode's.  Dependencies cross kernel boundaries only.  The algebra: tests/tail_seg_model.py.
+__global__ __launch_bounds__(kSegBlock) void tail_seg_scan_kernel(const uint8_t* __restrict__ in,
+                                                                  const uint64_t* __restrict__ off,
+                                                                  const uint64_t* __restrict__ len,
+                                                                  uint64_t* __restrict__ tail,
+                                                                  uint64_t* __restrict__ ulen,
+                                                                  uint32_t* __restrict__ status, u32 n,
+                                                                  const u32* __restrict__ seg_first, u32 maxseg,
+                                                                  u32 sb, const uint4* __restrict__ summ) {
+    __shared__ __attribute__((aligned(16))) uint8_t slots_all[kSegWaves * 2 * kSlot];
+    __shared__ __attribute__((aligned(16))) DecEntry tbl[256];
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    for (u32 k = threadIdx.x; k < 256u; k += kSegBlock) tbl[k] = kDecTable.e[k];
+    __syncthreads();
+    const u32 b = blockIdx.x * kSegWaves + wid;
+    if (b >= n) return;
+    const uint64_t C64 = len[b];
+    const uint8_t* src = in + off[b];
+    const u32 s0 = seg_lo(seg_first, b), s1 = seg_hi(seg_first, b, len, sb);
+    u32 bad = ((uintptr_t)src & 15u) ? RLE_STATUS_MISALIGNED : 0u;
+    if (C64 > kMaxBufferBytes || s1 > maxseg) bad |= RLE_STATUS_TOOLARGE;
+    uint64_t w = 0u, U = 0u;
+    if (!bad && C64) {
+        const u32 C = (u32)C64;
+        u32 e = 0u, elast = 0u;   // the phase entering the window, and the one entering the last segment
+        bool stop = false;
+        for (u32 base = s0; base < s1; base += kWave) {
+            const u32 g = base + lane;
+            const bool valid = g < s1;
+            const uint4 sm = valid ? summ[g] : make_uint4(0u, 0u, 0u, 0u);
+            const u32 sel = valid ? (bfe(sm.w, 0, 2) | (bfe(sm.w, 2, 2) << 8) | (bfe(sm.w, 4, 2) << 16) | (3u << 24)) : kMapId;
+            const u32 incl = wave_scan_incl(sel, kMapId, OpMap());
+            const u32 ein = bfe(from_prev_lane(incl, kMapId), 8u * e, 8);   // the segment's taken entry phase
+            const u32 cnt = valid ? (ein == 0u ? sm.x : (ein == 1u ? sm.y : sm.z)) : 0u;
+            stop |= __builtin_amdgcn_ballot_w64(valid && ((sm.w >> (8u + ein)) & 1u)) != 0ull;
+            U += wave_sum(cnt);   // a window decodes to less than 64 * 17 * 3024 bytes
+            elast = readlane(ein, s1 - 1u - base < kWave ? s1 - 1u - base : kWave - 1u);
+            e = bfe(readlane(incl, 63), 8u * e, 8);
+        }
+        u32 q0, q1;
+        seg_range(s1 - 1u - s0, s1 - s0, C, sb, q0, q1);
+        u32 last = q0 + elast, d = elast;
+        if (!stop) {
+            const u32x4 rsi = make_rsrc(src, (C + 15u) & ~15u);
+            const DecK kc = dec_k();
+            constexpr uint64_t kOwned = (1ull << kOwnLanes) - 1ull;
+            stop = walk_tiles(rsi, q0, ntiles_for(q1 - q0), lane, slots_all + wid * 2 * kSlot,
+                              [&](u32 t, const uint8_t* cs, const Refill& nx) {
+                const u32 pos = q0 + t * kTileStep;
+                const u32x4 cur = *reinterpret_cast<const u32x4*>(cs + 16u * lane);
+                nx();   // the slot is free once read
+                const DecPrep pr = dec_prepare(cur, pos, C, C, lane, tbl, kc);
+                const DecLen ln = dec_lengths(pr, d);
+                if (__builtin_amdgcn_ballot_w64(ln.serial_lane) & kOwned) return ~0u;
+                tail_tile_last(ln, pos, kc, last);
+                d = bfe(readlane(pr.incl, kOwnLanes - 1u), 8u * d, 8);
+                return 0u;
+            });
+            vm_drain();
+        }
+        if (!stop) w = tail_close(src, C, last);
+        if (!w) {
+            bad = RLE_STATUS_NOTCANON;
+            U = 0u;
+        }
+    }
+    if (lane == 0) {
+        tail[b] = w;
+        if (ulen) ulen[b] = U;
+        if (status) status[b] = bad;
+    }
+}
+
 }  // namespace rle
 
 extern "C" size_t rle_append_slot_bytes(uint64_t C, uint64_t A) { return (size_t)rle::append_slot_bytes(C, A); }
@@ -514,5 +617,29 @@ extern "C" int rle_append_batch_device_seg(void* d_streams, const uint64_t* d_of
     hipLaunchKernelGGL(rle::append_seg_write_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, streams, d_off, newb,
                        d_new_off, d_new_len, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, entry, sh.plan, sh.bflag,
                        sh.summ);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+
+// The workspace: the segmented decode's carve-up, nothing of the scan's own.
+extern "C" size_t rle_tail_seg_workspace_bytes(uint32_t n, uint64_t total_in_bytes) {
+    rle::SegShape sh;
+    rle::seg_prologue(nullptr, 0, n, total_in_bytes, 0, &sh);
+    return sh.bytes;
+}
+
+extern "C" int rle_tail_batch_device_seg(const void* d_in, const uint64_t* d_off, const uint64_t* d_len,
+                                         uint64_t* d_tail, uint64_t* d_ulen, uint32_t* d_status, uint32_t n,
+                                         uint64_t total_in_bytes, void* d_workspace, size_t workspace_bytes,
+                                         void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_in || !d_off || !d_len || !d_tail) return RLE_E_INVAL;
+    rle::SegShape sh;
+    if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_in_bytes, 0, &sh)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    const uint8_t* in = (const uint8_t*)d_in;
+    rle::seg_launch_plan_map(d_len, n, sh, s);
+    rle::seg_launch_dec_summary(in, d_off, d_len, n, sh, s);
+    hipLaunchKernelGGL(rle::tail_seg_scan_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, in, d_off,
+                       d_len, d_tail, d_ulen, d_status, n, sh.seg_first, sh.maxseg, sh.sb, sh.summ);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }

@@ -5,8 +5,9 @@
 // the segmented codec from it, and csrc/rle_fileops.hip the segmented append
 // (rle_append_batch_device_seg), whose view enters a file's first segment with the state an append
 // carries and runs every later segment as the encode does.  The host side at the end declares the
-// launch shape and prologue that every segmented entry point shares.
-// The algebra: tests/seg_model.py, tests/append_seg_model.py.
+// launch shape and prologue that every segmented entry point shares, and the decode's summary launch,
+// which the segmented tail scan (rle_tail_batch_device_seg, csrc/rle_fileops.hip) makes as well.
+// The algebra: tests/seg_model.py, tests/append_seg_model.py, tests/tail_seg_model.py.
 #pragma once
 #include "rle_device.h"
 
@@ -397,5 +398,11 @@ int seg_prologue(void* d_workspace, size_t workspace_bytes, uint32_t n, uint64_t
 // The single-pass variants have the plan clear their flags, ticket and per-buffer words as well.
 void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hipStream_t s,
                          uint32_t* sflag = nullptr, uint32_t* ticket = nullptr, uint32_t* bclear = nullptr);
+// The decode's summary launch over the streams `in + off[i]` of `len[i]` bytes into the shape's
+// summaries (dec_seg_summary_kernel: per segment and entry phase 0..2 the decoded bytes in .x .y .z,
+// the exit phases in .w bits 0..5 and the phases whose parse stops in bits 8..10).  The segmented
+// tail scan (csrc/rle_fileops.hip) reads the same words.
+void seg_launch_dec_summary(const uint8_t* in, const uint64_t* off, const uint64_t* len, uint32_t n,
+                            const SegShape& sh, hipStream_t s);
 inline uint32_t seg_buf_grid(uint32_t n) { return (n + kSegWaves - 1u) / kSegWaves; }   // one wave per buffer
 }  // namespace rle

@@ -1082,6 +1082,11 @@ void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hi
     hipLaunchKernelGGL(seg_map_kernel, dim3((sh.maxseg + kMapBlock - 1) / kMapBlock), dim3(kMapBlock), 0, s,
                        sh.seg_first, n, sh.maxseg, sh.seg_buf);
 }
+void seg_launch_dec_summary(const uint8_t* in, const uint64_t* off, const uint64_t* len, uint32_t n,
+                            const SegShape& sh, hipStream_t s) {
+    hipLaunchKernelGGL(dec_seg_summary_kernel, dim3(sh.grid), dim3(kSegBlock), 0, s, in, off, len, n, sh.seg_first,
+                       sh.seg_buf, sh.maxseg, sh.sb, sh.summ);
+}
 }  // namespace rle
 
 extern "C" size_t rle_seg_workspace_bytes(uint32_t n, uint64_t total_in_bytes) {
@@ -1165,8 +1170,7 @@ extern "C" int rle_decode_batch_device_seg(const void* d_in, const uint64_t* d_i
     }
 #endif
     rle::seg_launch_plan_map(d_in_len, n, sh, s);
-    hipLaunchKernelGGL(rle::dec_seg_summary_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len,
-                       n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, sh.summ);
+    rle::seg_launch_dec_summary(in, d_in_off, d_in_len, n, sh, s);
     hipLaunchKernelGGL(rle::dec_seg_scan_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, in, d_in_off,
                        d_in_len, out, d_out_off, d_out_len, d_out_cap, d_status, n, sh.seg_first, sh.maxseg, sh.sb,
                        sh.summ, sh.plan, sh.bflag);

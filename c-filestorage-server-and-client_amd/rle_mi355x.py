@@ -116,6 +116,10 @@ def lib():
     L.rle_append_seg_workspace_bytes.argtypes = [u32, u64]
     L.rle_append_batch_device_seg.restype = ctypes.c_int
     L.rle_append_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, sz, vp]
+    L.rle_tail_seg_workspace_bytes.restype = sz
+    L.rle_tail_seg_workspace_bytes.argtypes = [u32, u64]
+    L.rle_tail_batch_device_seg.restype = ctypes.c_int
+    L.rle_tail_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, u32, u64, vp, sz, vp]
     L.rle_mi355x_set_coop_mode.restype = ctypes.c_int
     L.rle_mi355x_set_coop_mode.argtypes = [ctypes.c_int]
     u32p = ctypes.POINTER(u32)
@@ -399,6 +403,30 @@ def tail_batch(d_in, off, length, tail, ulen=None, status=None, stream=None):
                                      off.numel(), _stream_ptr(stream))
     if rc != RLE_OK:
         raise RLEError(f"rle_tail_batch_device failed: {rc}")
+
+
+def tail_seg_workspace(n: int, total_in_bytes: int, device=None):
+    """A device workspace for tail_batch_seg (caller-owned, reusable across calls on one stream)."""
+    import torch
+    nb = int(lib().rle_tail_seg_workspace_bytes(n, int(total_in_bytes)))
+    return torch.empty(nb + 256, dtype=torch.uint8, device=device if device is not None else "cuda")
+
+
+def tail_batch_seg(d_in, off, length, tail, ulen=None, status=None, total_in_bytes=None, ws=None, stream=None):
+    """rle_tail_batch_device_seg: tail_batch with several waves per stream, for streams that are large
+    next to the batch.  total_in_bytes (>= the sum of length; default: that sum) sizes the segment
+    tables; ws: from tail_seg_workspace (default: a fresh one).  The default total_in_bytes
+    synchronises (the sum is read back from the device): a call captured into a graph must pass
+    total_in_bytes and ws."""
+    n = off.numel()
+    total = int(length.sum().item()) if total_in_bytes is None else int(total_in_bytes)
+    if ws is None:
+        ws = tail_seg_workspace(n, total, d_in.device)
+    wp, wn = _ws_ptr(ws)
+    rc = lib().rle_tail_batch_device_seg(_ptr(d_in), _ptr(off), _ptr(length), _ptr(tail), _ptr(ulen), _ptr(status),
+                                         n, total, wp, wn, _stream_ptr(stream))
+    if rc != RLE_OK:
+        raise RLEError(f"rle_tail_batch_device_seg failed: {rc}")
 
 
 def append_batch(d_streams, off, length, cap, ulen, d_new, new_off, new_len, status=None, tail=None, stream=None):

@@ -26,6 +26,7 @@
  *
  * Graph capture (tests/test_gpu_graph_replay.py): the batch entry points -- rle_encode_batch_device,
  * rle_decode_batch_device, their *_sized and *_sized_flags forms, the *_seg forms,
+ * rle_tail_batch_device_seg (tests/test_gpu_tail_seg_replay.py),
  * rle_append_batch_device, rle_append_batch_device_seg and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
  * (global) capture mode, and the graph replayed any number of times.  The host freezes at capture
  * what it decides itself: the kernel form (from n, the max_* hints and the cooperative mode), the
@@ -221,10 +222,37 @@ size_t rle_append_slot_bytes(uint64_t C, uint64_t A);
  * RLE_STATUS_OK: d_tail[i] = t | r << 32 and d_ulen[i] = U (64-bit: it may exceed 2 GiB); C = 0 is
  * OK with tail 0 and ulen 0.  RLE_STATUS_NOTCANON, RLE_STATUS_MISALIGNED (the stream's address) and
  * RLE_STATUS_TOOLARGE (C > RLE_MAX_BUFFER_BYTES): tail 0 and ulen 0.  d_ulen and d_status may be
- * NULL.  One wave per stream is the only form: a segmented scan for very large single streams is
- * not provided. */
+ * NULL.  One wave per stream walks the stream's tiles one after another: for streams that are large
+ * next to the batch, rle_tail_batch_device_seg below spreads the same scan over many waves. */
 int rle_tail_batch_device(const void* d_in, const uint64_t* d_off, const uint64_t* d_len, uint64_t* d_tail,
                           uint64_t* d_ulen, uint32_t* d_status, uint32_t n, void* stream);
+
+/* The same scan with several waves per stream ("segmented scan"): each stream is cut
+ * into the segments of rle_decode_batch_device_seg (rle_seg_segment_bytes(total_in_bytes) bytes each,
+ * the last one taking a remainder of 1-2 bytes) and goes through its summary launch; one wave per
+ * stream then composes the segments' token phases, sums the decoded length in 64 bits, and walks
+ * the stream's last segment, where the final token starts, for the tail word.  The parse, the tail
+ * word, d_ulen, the status bits and the results of refused streams (tail 0, ulen 0) are those of
+ * rle_tail_batch_device, word for word; d_ulen and d_status may be NULL.  Plus:
+ *   total_in_bytes  >= the sum of the n stream lengths (sizes the segment tables; a stream whose
+ *                   segments do not fit gets RLE_STATUS_TOOLARGE, tail 0, ulen 0)
+ *   d_workspace     caller-owned device memory of at least rle_tail_seg_workspace_bytes(n,
+ *                   total_in_bytes) = rle_seg_workspace_bytes(n, total_in_bytes) bytes (the decode's
+ *                   tables; the scan keeps no record of its own), 256-byte aligned, not used by
+ *                   another launch in flight
+ * Decided on the host before anything is launched: n == 0 is RLE_OK; a NULL d_in, d_off, d_len,
+ * d_tail or d_workspace, or workspace_bytes below that size, is RLE_E_INVAL.
+ * rle_tail_batch_device never routes here: the caller picks the form.
+ * Measured on one MI355X (profiles/tail_seg.json), one-wave against segmented: one
+ * 1 MiB stream 531-533 us against 13-19 us, 64 of them 568-573 us against 38-47 us, one 64 KiB stream
+ * 36-37 us against 12-14 us; 4096 streams of 4 KiB 10-12 us against 29-33 us and 4096 streams of 64 KiB
+ * 81-87 us against 89-107 us, where the one-wave form wins.  The crossover follows the number of
+ * streams, not their size: use this form for a few dozen streams or fewer of tens of KiB and more;
+ * a batch of a thousand streams fills the chip with one wave each. */
+size_t rle_tail_seg_workspace_bytes(uint32_t n, uint64_t total_in_bytes);
+int rle_tail_batch_device_seg(const void* d_in, const uint64_t* d_off, const uint64_t* d_len, uint64_t* d_tail,
+                              uint64_t* d_ulen, uint32_t* d_status, uint32_t n, uint64_t total_in_bytes,
+                              void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Append in place, one wave per file: file i's stream is d_streams + d_off[i], d_len[i] = C bytes in
  * a slot of d_cap[i] bytes; its new content is d_new + d_new_off[i], d_new_len[i] = A bytes (readable
@@ -268,7 +296,7 @@ int rle_append_batch_device(void* d_streams, const uint64_t* d_off, uint64_t* d_
  * 1 MiB append 838-1579 us against 22-23 us, 64 of them 876-1628 us against 72-97 us, one 64 KiB append
  * 57-103 us against 20 us; 4096 appends of 4 KiB 17-23 us against 45-50 us, where the one-wave form
  * wins.  The crossover lies between a few KiB and tens of KiB of new content per file.
- * The tail scan has no segmented form, and RLEappend (include/rle_fileops.h) does not use this one. */
+ * RLEappend (include/rle_fileops.h) does not use this one. */
 size_t rle_append_seg_workspace_bytes(uint32_t n, uint64_t total_new_bytes);
 int rle_append_batch_device_seg(void* d_streams, const uint64_t* d_off, uint64_t* d_len, const uint64_t* d_cap,
                                 uint64_t* d_ulen, uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
