@@ -13,7 +13,10 @@
 // rle_append_batch_device), and the append's segmented form for large new content
 // (rle_append_batch_device_seg: several waves per file, on the segmented encode's device code) and
 // the scan's segmented form for large stored streams (rle_tail_batch_device_seg: the segmented
-// decode's summaries and a per-stream scan of its own).
+// decode's summaries and a per-stream scan of its own); and the append's new length before anything
+// is stored, with the append into a slot that merely fits (rle_append_size_batch_device,
+// rle_append_fit_batch_device and their _seg forms: append_fit_kernel and the fit variants of the
+// segmented entry and scan kernels).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -311,6 +314,120 @@ __global__ __launch_bounds__(kFileBlock) void append_kernel(uint8_t* streams, co
     }
 }
 
+// rle_append_size_batch_device (kCommit false) and rle_append_fit_batch_device (kCommit true): the
+// length C' the append above would leave, known before anything is stored, and the append whose only
+// capacity condition is cap >= C'.  One wave per file, append_kernel's checks in its order without
+// the capacity one.  The size walk is a segment summary of the virtual buffer's whole range [vs, Uv)
+// (enc_seg_summarize: the tiles' analysis, no staging and no stores), entered as append_kernel's walk
+// is entered (previous byte c, run phase r - 1 at position 15) and closed as enc_seg_window closes a
+// segment: C' = the offset behind the final token as it stands with r + e, the tokens starting in
+// the entering run piece (enc_piece_count), the tokens from the first boundary on.  kCommit: a file
+// whose slot holds the worst case (cap >= rle_append_slot_bytes) cannot overflow and skips the size
+// walk, so it costs what append_kernel costs; any other file is sized first, and nothing of it is
+// stored before cap >= C' is known.  The write walk is append_kernel's; it starts only when every
+// memory operation of the size walk has completed (vm_drain: walk_tiles counts from zero).
+template <bool kCommit>
+__global__ __launch_bounds__(kFileBlock) void append_fit_kernel(uint8_t* streams, const uint64_t* __restrict__ off,
+                                                                uint64_t* len, const uint64_t* __restrict__ cap,
+                                                                uint64_t* ulen, uint64_t* tail,
+                                                                const uint8_t* __restrict__ newb,
+                                                                const uint64_t* __restrict__ new_off,
+                                                                const uint64_t* __restrict__ new_len,
+                                                                uint64_t* __restrict__ need_out, uint32_t* status,
+                                                                uint32_t n) {
+    __shared__ __attribute__((aligned(16))) uint8_t slots_all[kFileWaves * 2 * kSlot];
+    __shared__ __attribute__((aligned(16))) uint8_t stage_all[kCommit ? kFileWaves * kEncStage : 16];
+    __shared__ __attribute__((aligned(16))) u32 elut[kCommit ? kInsWaveWords : 4];   // enc_tile_fast's selectors
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    if constexpr (kCommit) {
+        for (u32 k = threadIdx.x; k < kInsWaveWords; k += kFileBlock) elut[k] = kEncInsLut.s[k];
+        __syncthreads();
+    }
+    const u32 b = blockIdx.x * kFileWaves + wid;
+    if (b >= n) return;
+    // every word of the file is loaded here, before the walks' hand-counted memory operations
+    const uint64_t C64 = len[b], A64 = new_len[b], w = tail[b], soff = off[b], noff = new_off[b];
+    const uint64_t cp = kCommit ? cap[b] : 0u;
+    const uint64_t ul = (kCommit && ulen) ? ulen[b] : 0u;
+    uint8_t* dst = streams + soff;
+    const uint8_t* nw = newb + noff;
+    const uint64_t slot = append_slot_bytes(C64, A64);
+    u32 bad = slot ? 0u : RLE_STATUS_TOOLARGE;
+    if (((uintptr_t)dst | (uintptr_t)nw) & 15u) bad |= RLE_STATUS_MISALIGNED;
+    const u32 C = (u32)C64, A = (u32)A64;
+    const u32 t = (u32)w, r = (u32)(w >> 32);
+    u32 c = 0u;
+    if (!bad) {
+        // the tail word describes the stream's last bytes (as in append_kernel)
+        if (w == 0u) {
+            if (C) bad = RLE_STATUS_NOTCANON;
+        } else if ((w >> 36) || r < 1u || r > 9u || C64 != (uint64_t)t + (r == 1u ? 1u : 3u)) {
+            bad = RLE_STATUS_NOTCANON;
+        } else {
+            c = uniform((u32)dst[t]);
+            if (r > 1u && (uniform((u32)dst[t + 1u]) != c || uniform((u32)dst[t + 2u]) != 0x30u + r))
+                bad = RLE_STATUS_NOTCANON;
+        }
+    }
+    if (bad || A == 0u) {   // refused (0), or nothing to append (C): the file is left as it is
+        if (lane == 0) {
+            need_out[b] = bad ? 0u : C64;
+            if (status) status[b] = bad;
+        }
+        return;
+    }
+    u32 vs = 0u, outp = 0u, rs = 0u, e = 0u;
+    if (C) {
+        const u32 lim = A < 9u - r ? A : 9u - r;
+        const bool eq = lane < lim && nw[lane] == (uint8_t)c;
+        e = (u32)__builtin_ctzll(__builtin_amdgcn_ballot_w64(!eq));   // <= lim <= 8
+        vs = 16u;
+        outp = t + (r + e == 1u ? 1u : 3u);
+        rs = 16u - r;
+    }
+    const u32 Uv = vs + A;
+    const uint8_t* vsrc = reinterpret_cast<const uint8_t*>((uintptr_t)nw - vs);
+    const uint8_t* slots = slots_all + wid * 2 * kSlot;
+    u32 bound = (u32)slot;   // the bytes of the slot the stores may reach
+    if (!kCommit || cp < slot) {
+        const uint4 sm = enc_seg_summarize(vsrc, Uv, vs, Uv, lane, slots, SegEntry{vs != 0u, c});
+        const u32 piece = vs ? enc_piece_count(uniform(sm.x), r - 1u, uniform(sm.w)) : 0u;
+        const u32 cnew = outp + piece + uniform(sm.z);
+        if (!kCommit || cp < cnew) {
+            if (lane == 0) {
+                need_out[b] = cnew;
+                if (status) status[b] = kCommit ? RLE_STATUS_NOFIT : RLE_STATUS_OK;
+            }
+            return;
+        }
+        bound = (u32)cp;
+        vm_drain();   // the write walk counts its own operations only
+    }
+    if constexpr (kCommit) {
+        if (e && lane < 3u) dst[t + lane] = (uint8_t)(lane < 2u ? c : 0x30u + r + e);
+        const u32x4 rsi = make_rsrc(vsrc, (Uv + 15u) & ~15u);
+        const u32x4 rso = make_rsrc(dst, bound);
+        uint8_t* stage = stage_all + wid * kEncStage;
+        EncState st{outp, outp & ~15u, c << 24, rs, outp & 15u, false, {}};
+        const EncK kc = enc_k();
+        u32 final_rs = rs;
+        walk_tiles(rsi, vs, ntiles_for(A), lane, slots, [&](u32 k, const uint8_t* cs, const Refill& nx) {
+            return app_tile(cs, nx, vs + k * kTileStep, Uv, lane, stage, dst, rso, st, kc, elut, final_rs);
+        });
+        // the final partial chunk, as in append_kernel
+        if (lane >= st.head && lane < st.out_pos - st.flushed) dst[st.flushed + lane] = stage[16u + lane];
+        if (lane == 0) {
+            const u32 rn = (Uv - final_rs - 1u) % 9u + 1u;   // the new final token's count
+            len[b] = st.out_pos;
+            tail[b] = (uint64_t)(st.out_pos - (rn == 1u ? 1u : 3u)) | ((uint64_t)rn << 32);
+            if (ulen) ulen[b] = ul + A;
+            need_out[b] = st.out_pos;
+            if (status) status[b] = RLE_STATUS_OK;
+        }
+    }
+}
+
 // ================================================================ segmented append
 // rle_append_batch_device_seg: the same append with several waves per file, for new content that is
 // large next to the batch (one wave walks a 1 MiB append tile after tile while the chip idles).  The
@@ -355,23 +472,24 @@ __device__ __forceinline__ EncView app_view(const uint4* entry, uint8_t* streams
                    en.need, !en.bad && A64 != 0u};
 }
 
-__global__ __launch_bounds__(kEntryBlock) void append_seg_entry_kernel(const uint8_t* __restrict__ streams,
-                                                                       const uint64_t* __restrict__ off,
-                                                                       const uint64_t* __restrict__ len,
-                                                                       const uint64_t* __restrict__ cap,
-                                                                       const uint64_t* __restrict__ tail,
-                                                                       const uint8_t* __restrict__ newb,
-                                                                       const uint64_t* __restrict__ new_off,
-                                                                       const uint64_t* __restrict__ new_len, u32 n,
-                                                                       uint4* __restrict__ entry) {
+// The entry record of file b.  kFit (the size and fit forms): no capacity check, MISALIGNED means
+// addresses only, and the recorded bound is min(cap, slot bytes) (cap null, the size form: the slot
+// bytes), which the fit scan compares C' with and the writers' store descriptor is made from.
+template <bool kFit>
+__device__ __forceinline__ void app_seg_entry(const uint8_t* __restrict__ streams, const uint64_t* __restrict__ off,
+                                              const uint64_t* __restrict__ len, const uint64_t* __restrict__ cap,
+                                              const uint64_t* __restrict__ tail, const uint8_t* __restrict__ newb,
+                                              const uint64_t* __restrict__ new_off,
+                                              const uint64_t* __restrict__ new_len, u32 n,
+                                              uint4* __restrict__ entry) {
     const u32 b = blockIdx.x * kEntryBlock + threadIdx.x;
     if (b >= n) return;
-    const uint64_t C64 = len[b], A64 = new_len[b], cp = cap[b], w = tail[b];
+    const uint64_t C64 = len[b], A64 = new_len[b], cp = (kFit && !cap) ? ~0ull : cap[b], w = tail[b];
     const uint8_t* dst = streams + off[b];
     const uint8_t* nw = newb + new_off[b];
     const uint64_t need = append_slot_bytes(C64, A64);
     u32 bad = need ? 0u : RLE_STATUS_TOOLARGE;
-    if ((((uintptr_t)dst | (uintptr_t)nw) & 15u) || (need && cp < need)) bad |= RLE_STATUS_MISALIGNED;
+    if ((((uintptr_t)dst | (uintptr_t)nw) & 15u) || (!kFit && need && cp < need)) bad |= RLE_STATUS_MISALIGNED;
     const u32 t = (u32)w, r = (u32)(w >> 32);
     u32 c = 0u, e = 0u, vs = 0u;
     if (!bad) {
@@ -392,8 +510,19 @@ __global__ __launch_bounds__(kEntryBlock) void append_seg_entry_kernel(const uin
         vs = 16u;
         x = c | (r << 8) | (e << 16) | (vs << 24);
     }
-    entry[b] = make_uint4(x, bad, t, (u32)need);
+    entry[b] = make_uint4(x, bad, t, (u32)(kFit && cp < need ? cp : need));
 }
+#define RLE_APP_ENTRY_ARGS                                                                                       \
+    const uint8_t *__restrict__ streams, const uint64_t *__restrict__ off, const uint64_t *__restrict__ len,    \
+        const uint64_t *__restrict__ cap, const uint64_t *__restrict__ tail, const uint8_t *__restrict__ newb,  \
+        const uint64_t *__restrict__ new_off, const uint64_t *__restrict__ new_len, u32 n, uint4 *__restrict__ entry
+__global__ __launch_bounds__(kEntryBlock) void append_seg_entry_kernel(RLE_APP_ENTRY_ARGS) {
+    app_seg_entry<false>(streams, off, len, cap, tail, newb, new_off, new_len, n, entry);
+}
+__global__ __launch_bounds__(kEntryBlock) void append_fit_seg_entry_kernel(RLE_APP_ENTRY_ARGS) {
+    app_seg_entry<true>(streams, off, len, cap, tail, newb, new_off, new_len, n, entry);
+}
+#undef RLE_APP_ENTRY_ARGS
 
 __global__ __launch_bounds__(kSegBlock) void append_seg_summary_kernel(const uint8_t* __restrict__ newb,
                                                                        const uint64_t* __restrict__ new_off,
@@ -453,6 +582,66 @@ __global__ __launch_bounds__(kSegBlock) void append_seg_scan_kernel(uint8_t* str
         if (ulen) ulen[b] = ul + A;
         if (status) status[b] = RLE_STATUS_OK;
         bflag[b] = 0u;
+    }
+}
+
+// The scan of the size and fit forms: append_seg_scan_kernel with C' = cy.off to need_out.  kCommit
+// (rle_append_fit_batch_device_seg): a file whose recorded bound, min(cap, slot bytes), is below C'
+// is refused (NOFIT, kFlagSkip) before the final token or any word of it is written.  Else
+// (rle_append_size_batch_device_seg): need_out and the status only; no write launch follows, and
+// streams, off, ulen are null.
+template <bool kCommit>
+__global__ __launch_bounds__(kSegBlock) void append_fit_seg_scan_kernel(
+    uint8_t* streams, const uint64_t* __restrict__ off, uint64_t* len, uint64_t* ulen, uint64_t* tail,
+    const uint64_t* __restrict__ new_len, uint64_t* __restrict__ need_out, uint32_t* status, u32 n,
+    const u32* __restrict__ seg_first, u32 maxseg, u32 sb, const uint4* __restrict__ entry,
+    const uint4* __restrict__ summ, uint2* __restrict__ plan, u32* __restrict__ bflag) {
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 b = blockIdx.x * kSegWaves + uniform(threadIdx.x / kWave);
+    if (b >= n) return;
+    const AppEntry en = app_entry(entry, b);
+    const uint64_t A64 = new_len[b];
+    const uint64_t ul = (kCommit && ulen) ? ulen[b] : 0u;
+    const u32 s0 = seg_lo(seg_first, b), s1 = seg_hi(seg_first, b, new_len, sb);
+    const u32 bad = en.bad | (s1 > maxseg ? (u32)RLE_STATUS_TOOLARGE : 0u);
+    if (bad || A64 == 0u) {   // refused (0), or nothing to append (C): the file is left as it is
+        if (lane == 0) {
+            need_out[b] = bad ? 0u : len[b];
+            if (status) status[b] = bad;
+            bflag[b] = kFlagSkip;
+        }
+        return;
+    }
+    const u32 A = (u32)A64, rr = en.r + en.e;
+    EncCarry cy{en.vs ? 17u - en.r : 0u, en.vs ? en.t + (rr == 1u ? 1u : 3u) : 0u};
+    for (u32 base = s0; base < s1; base += kWave) {
+        const u32 g = base + lane;
+        const bool valid = g < s1;
+        const uint4 sm = valid ? summ[g] : make_uint4(0u, 0u, 0u, 0u);
+        const uint2 pl = enc_seg_window(sm, valid, en.vs + (g - s0) * sb, cy);
+        if (kCommit && valid) plan[g] = pl;
+    }
+    if (!kCommit || cy.off > en.need) {   // nothing of the file is stored
+        if (lane == 0) {
+            need_out[b] = cy.off;
+            if (status) status[b] = kCommit ? (u32)RLE_STATUS_NOFIT : (u32)RLE_STATUS_OK;
+            bflag[b] = kFlagSkip;
+        }
+        return;
+    }
+    if constexpr (kCommit) {
+        uint8_t* dst = streams + off[b];
+        if (en.e && lane < 3u) dst[en.t + lane] = (uint8_t)(lane < 2u ? en.c : 0x30u + rr);
+        if (lane == 0) {
+            const u32 Uv = en.vs + A, frs = cy.lb1 ? cy.lb1 - 1u : 0u;   // the final run's start
+            const u32 rn = (Uv - frs - 1u) % 9u + 1u;                    // the new final token's count
+            len[b] = cy.off;
+            tail[b] = (uint64_t)(cy.off - (rn == 1u ? 1u : 3u)) | ((uint64_t)rn << 32);
+            if (ulen) ulen[b] = ul + A;
+            need_out[b] = cy.off;
+            if (status) status[b] = RLE_STATUS_OK;
+            bflag[b] = 0u;
+        }
     }
 }
 
@@ -618,6 +807,93 @@ extern "C" int rle_append_batch_device_seg(void* d_streams, const uint64_t* d_of
                        d_new_off, d_new_len, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, entry, sh.plan, sh.bflag,
                        sh.summ);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+
+extern "C" int rle_append_size_batch_device(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                                            const uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
+                                            const uint64_t* d_new_len, uint64_t* d_need, uint32_t* d_status,
+                                            uint32_t n, void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_streams || !d_off || !d_len || !d_tail || !d_new || !d_new_off || !d_new_len || !d_need) return RLE_E_INVAL;
+    // the size instantiation stores to d_need and d_status only
+    hipLaunchKernelGGL(rle::append_fit_kernel<false>, dim3((n + rle::kFileWaves - 1u) / rle::kFileWaves),
+                       dim3(rle::kFileBlock), 0, (hipStream_t)stream, (uint8_t*)const_cast<void*>(d_streams), d_off,
+                       const_cast<uint64_t*>(d_len), (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                       const_cast<uint64_t*>(d_tail), (const uint8_t*)d_new, d_new_off, d_new_len, d_need, d_status, n);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+
+extern "C" int rle_append_fit_batch_device(void* d_streams, const uint64_t* d_off, uint64_t* d_len,
+                                           const uint64_t* d_cap, uint64_t* d_ulen, uint64_t* d_tail,
+                                           const void* d_new, const uint64_t* d_new_off, const uint64_t* d_new_len,
+                                           uint64_t* d_need, uint32_t* d_status, uint32_t n, void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_streams || !d_off || !d_len || !d_cap || !d_tail || !d_new || !d_new_off || !d_new_len || !d_need)
+        return RLE_E_INVAL;
+    hipLaunchKernelGGL(rle::append_fit_kernel<true>, dim3((n + rle::kFileWaves - 1u) / rle::kFileWaves),
+                       dim3(rle::kFileBlock), 0, (hipStream_t)stream, (uint8_t*)d_streams, d_off, d_len, d_cap, d_ulen,
+                       d_tail, (const uint8_t*)d_new, d_new_off, d_new_len, d_need, d_status, n);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+
+// The segmented size and fit forms: plan, map, entry (without the capacity check), summary, scan,
+// and for the fit form the write.  d_cap null: the size form.
+static int append_fit_seg(void* d_streams, const uint64_t* d_off, uint64_t* d_len, const uint64_t* d_cap,
+                          uint64_t* d_ulen, uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
+                          const uint64_t* d_new_len, uint64_t* d_need, uint32_t* d_status, uint32_t n,
+                          uint64_t total_new_bytes, void* d_workspace, size_t workspace_bytes, void* stream,
+                          bool commit) {
+    rle::SegShape sh;
+    const size_t records = sizeof(uint4) * (size_t)n;   // one entry record per file behind the encode's tables
+    if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_new_bytes, records, &sh)) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    uint4* const entry = static_cast<uint4*>(sh.extra);
+    uint8_t* streams = (uint8_t*)d_streams;
+    const uint8_t* newb = (const uint8_t*)d_new;
+    rle::seg_launch_plan_map(d_new_len, n, sh, s);
+    hipLaunchKernelGGL(rle::append_fit_seg_entry_kernel, dim3((n + rle::kEntryBlock - 1u) / rle::kEntryBlock),
+                       dim3(rle::kEntryBlock), 0, s, streams, d_off, d_len, d_cap, d_tail, newb, d_new_off, d_new_len, n,
+                       entry);
+    hipLaunchKernelGGL(rle::append_seg_summary_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, newb, d_new_off,
+                       d_new_len, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, entry, sh.summ);
+    if (!commit) {
+        hipLaunchKernelGGL(rle::append_fit_seg_scan_kernel<false>, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0,
+                           s, (uint8_t*)nullptr, (const uint64_t*)nullptr, d_len, (uint64_t*)nullptr, d_tail, d_new_len,
+                           d_need, d_status, n, sh.seg_first, sh.maxseg, sh.sb, entry, sh.summ, sh.plan, sh.bflag);
+        return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+    }
+    hipLaunchKernelGGL(rle::append_fit_seg_scan_kernel<true>, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, streams,
+                       d_off, d_len, d_ulen, d_tail, d_new_len, d_need, d_status, n, sh.seg_first, sh.maxseg, sh.sb,
+                       entry, sh.summ, sh.plan, sh.bflag);
+    hipLaunchKernelGGL(rle::append_seg_write_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, streams, d_off, newb,
+                       d_new_off, d_new_len, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, entry, sh.plan, sh.bflag,
+                       sh.summ);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+
+extern "C" int rle_append_size_batch_device_seg(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                                                const uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
+                                                const uint64_t* d_new_len, uint64_t* d_need, uint32_t* d_status,
+                                                uint32_t n, uint64_t total_new_bytes, void* d_workspace,
+                                                size_t workspace_bytes, void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_streams || !d_off || !d_len || !d_tail || !d_new || !d_new_off || !d_new_len || !d_need) return RLE_E_INVAL;
+    return append_fit_seg(const_cast<void*>(d_streams), d_off, const_cast<uint64_t*>(d_len), nullptr, nullptr,
+                          const_cast<uint64_t*>(d_tail), d_new, d_new_off, d_new_len, d_need, d_status, n,
+                          total_new_bytes, d_workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int rle_append_fit_batch_device_seg(void* d_streams, const uint64_t* d_off, uint64_t* d_len,
+                                               const uint64_t* d_cap, uint64_t* d_ulen, uint64_t* d_tail,
+                                               const void* d_new, const uint64_t* d_new_off, const uint64_t* d_new_len,
+                                               uint64_t* d_need, uint32_t* d_status, uint32_t n,
+                                               uint64_t total_new_bytes, void* d_workspace, size_t workspace_bytes,
+                                               void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_streams || !d_off || !d_len || !d_cap || !d_tail || !d_new || !d_new_off || !d_new_len || !d_need)
+        return RLE_E_INVAL;
+    return append_fit_seg(d_streams, d_off, d_len, d_cap, d_ulen, d_tail, d_new, d_new_off, d_new_len, d_need, d_status,
+                          n, total_new_bytes, d_workspace, workspace_bytes, stream, true);
 }
 
 // The workspace: the segmented decode's carve-up, nothing of the scan's own.

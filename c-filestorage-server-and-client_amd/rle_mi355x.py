@@ -28,6 +28,7 @@ RLE_STATUS_SERIAL = 0x100
 RLE_STATUS_SHORT = 0x400
 RLE_STATUS_INTERNAL = 0x800
 RLE_STATUS_NOTCANON = 0x1000
+RLE_STATUS_NOFIT = 0x2000
 RLE_TAIL_EMPTY = 0
 RLE_MAX_BUFFER_BYTES = 0x7FFFFFF0
 RLE_LAUNCH_STATUS_FLAG = 2
@@ -116,6 +117,14 @@ def lib():
     L.rle_append_seg_workspace_bytes.argtypes = [u32, u64]
     L.rle_append_batch_device_seg.restype = ctypes.c_int
     L.rle_append_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, sz, vp]
+    L.rle_append_size_batch_device.restype = ctypes.c_int
+    L.rle_append_size_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+    L.rle_append_size_batch_device_seg.restype = ctypes.c_int
+    L.rle_append_size_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, sz, vp]
+    L.rle_append_fit_batch_device.restype = ctypes.c_int
+    L.rle_append_fit_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+    L.rle_append_fit_batch_device_seg.restype = ctypes.c_int
+    L.rle_append_fit_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, sz, vp]
     L.rle_tail_seg_workspace_bytes.restype = sz
     L.rle_tail_seg_workspace_bytes.argtypes = [u32, u64]
     L.rle_tail_batch_device_seg.restype = ctypes.c_int
@@ -475,6 +484,70 @@ def append_batch_seg(d_streams, off, length, cap, ulen, d_new, new_off, new_len,
                                            _stream_ptr(stream))
     if rc != RLE_OK:
         raise RLEError(f"rle_append_batch_device_seg failed: {rc}")
+    return tail
+
+
+def append_size(d_streams, off, length, tail, d_new, new_off, new_len, need, status=None, stream=None):
+    """rle_append_size_batch_device: need[i] = the length append_batch would leave in length[i], and
+    nothing else is written (need: int64; tail: the streams' tail words, required)."""
+    rc = lib().rle_append_size_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(tail), _ptr(d_new),
+                                            _ptr(new_off), _ptr(new_len), _ptr(need), _ptr(status), off.numel(),
+                                            _stream_ptr(stream))
+    if rc != RLE_OK:
+        raise RLEError(f"rle_append_size_batch_device failed: {rc}")
+    return need
+
+
+def append_size_seg(d_streams, off, length, tail, d_new, new_off, new_len, need, status=None, total_new_bytes=None,
+                    workspace=None, stream=None):
+    """rle_append_size_batch_device_seg: append_size with several waves per file.  total_new_bytes and
+    workspace as in append_batch_seg (a captured call must pass both)."""
+    n = off.numel()
+    total = int(new_len.sum().item()) if total_new_bytes is None else int(total_new_bytes)
+    ws = workspace if workspace is not None else append_seg_workspace(n, total, d_new.device)
+    wp, wn = _ws_ptr(ws)
+    rc = lib().rle_append_size_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(tail), _ptr(d_new),
+                                                _ptr(new_off), _ptr(new_len), _ptr(need), _ptr(status), n, total, wp,
+                                                wn, _stream_ptr(stream))
+    if rc != RLE_OK:
+        raise RLEError(f"rle_append_size_batch_device_seg failed: {rc}")
+    return need
+
+
+def append_fit(d_streams, off, length, cap, ulen, d_new, new_off, new_len, need, status=None, tail=None, stream=None):
+    """rle_append_fit_batch_device: append_batch whose capacity rule is cap[i] >= the new length
+    (exact); need[i] receives that length, and a file that does not fit is refused with
+    RLE_STATUS_NOFIT, untouched.  tail=None: from a scan first, as in append_batch.  Returns the tail
+    tensor."""
+    if tail is None:
+        import torch
+        tail = torch.zeros(off.numel(), dtype=torch.int64, device=d_streams.device)
+        tail_batch(d_streams, off, length, tail, None, None, stream)
+    rc = lib().rle_append_fit_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen), _ptr(tail),
+                                           _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(need), _ptr(status),
+                                           off.numel(), _stream_ptr(stream))
+    if rc != RLE_OK:
+        raise RLEError(f"rle_append_fit_batch_device failed: {rc}")
+    return tail
+
+
+def append_fit_seg(d_streams, off, length, cap, ulen, d_new, new_off, new_len, need, status=None,
+                   total_new_bytes=None, workspace=None, tail=None, stream=None):
+    """rle_append_fit_batch_device_seg: append_fit with several waves per file.  total_new_bytes,
+    workspace and tail as in append_batch_seg (a captured call must pass all three)."""
+    n = off.numel()
+    if tail is None:
+        import torch
+        tail = torch.zeros(n, dtype=torch.int64, device=d_streams.device)
+        tail_batch(d_streams, off, length, tail, None, None, stream)
+    total = int(new_len.sum().item()) if total_new_bytes is None else int(total_new_bytes)
+    ws = workspace if workspace is not None else append_seg_workspace(n, total, d_streams.device)
+    wp, wn = _ws_ptr(ws)
+    rc = lib().rle_append_fit_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen),
+                                               _ptr(tail), _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(need),
+                                               _ptr(status), n, total, wp, wn, _stream_ptr(stream))
+    if rc != RLE_OK:
+        raise RLEError(f"rle_append_fit_batch_device_seg failed: {rc}")
     return tail
 
 

@@ -27,7 +27,9 @@
  * Graph capture (tests/test_gpu_graph_replay.py): the batch entry points -- rle_encode_batch_device,
  * rle_decode_batch_device, their *_sized and *_sized_flags forms, the *_seg forms,
  * rle_tail_batch_device_seg (tests/test_gpu_tail_seg_replay.py),
- * rle_append_batch_device, rle_append_batch_device_seg and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
+ * rle_append_batch_device, rle_append_batch_device_seg, rle_append_size_batch_device,
+ * rle_append_size_batch_device_seg, rle_append_fit_batch_device, rle_append_fit_batch_device_seg
+ * (tests/test_gpu_append_fit_replay.py) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
  * (global) capture mode, and the graph replayed any number of times.  The host freezes at capture
  * what it decides itself: the kernel form (from n, the max_* hints and the cooperative mode), the
  * grid, the segment length and table sizes (from the total_* hint), every pointer including the
@@ -70,6 +72,8 @@ extern "C" {
                                           not trusted */
 #define RLE_STATUS_NOTCANON    0x1000u /* tail scan / append: the stream, or the tail word given for it, is not
                                           what the encoder emits; nothing written */
+#define RLE_STATUS_NOFIT       0x2000u /* fit append: the slot is smaller than the stream the append would
+                                          leave; nothing written, d_need[i] says how much it takes */
 
 /* Worst-case compressed size of U bytes (every run of length 2: 3 bytes per 2 input bytes). */
 size_t rle_max_compressed_size(size_t U);
@@ -302,6 +306,64 @@ int rle_append_batch_device_seg(void* d_streams, const uint64_t* d_off, uint64_t
                                 uint64_t* d_ulen, uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
                                 const uint64_t* d_new_len, uint32_t* d_status, uint32_t n,
                                 uint64_t total_new_bytes, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- sizing an append before it is written ("Sizing an append before it is written")
+ * The reference looks at the new compressed size before it stores anything: a result larger than the
+ * store is refused and the file stays as it was, and other files are evicted until the new size fits
+ * (src/filesystemApi.c:777-798); only then is the content swapped (:811-814).  The appends above
+ * write in place and need a slot for the worst case.  These four give the exact new length first and
+ * append into a slot that merely fits.
+ *
+ * Contract, the same in all four.  Arguments are those of rle_append_batch_device (the size entries
+ * have no d_cap and no d_ulen, and write to nothing but d_need and d_status); d_need is required,
+ * d_status and d_ulen may be NULL.  Per file, in this order:
+ *   RLE_STATUS_TOOLARGE    rle_append_slot_bytes(C, A) == 0: the worst case must fit 32-bit offsets
+ *   RLE_STATUS_MISALIGNED  the stream or the new content is not 16-byte aligned (addresses only)
+ *   RLE_STATUS_NOTCANON    the tail word does not describe the stream's last bytes
+ *   A == 0                 RLE_STATUS_OK, nothing changes, d_need[i] = C; d_cap[i] is not consulted
+ *   otherwise              C' = the exact length of y[0, t) ‖ encode(c^r ‖ new), d_need[i] = C'.
+ *                          Size entries: RLE_STATUS_OK.  Fit entries: RLE_STATUS_OK when d_cap[i] >= C'
+ *                          (exact, not rounded), and then everything rle_append_batch_device writes
+ *                          is written, byte for byte and word for word; else RLE_STATUS_NOFIT.
+ * After every refusal, NOFIT included, the slot (the final token's three bytes too), d_len, d_ulen and
+ * d_tail are untouched; d_need[i] = 0 after TOOLARGE, MISALIGNED and NOTCANON, and C' after NOFIT.
+ * No byte at or past C' changes: a file that fits exactly may have another file's bytes right behind
+ * C'.  The store descriptor is bounded by min(d_cap[i], rle_append_slot_bytes(C, A)).
+ *
+ * One-wave forms: one wave per file.  The size entry walks the new bytes once (the encode's analysis:
+ * no staging, no stores).  The fit entry does the same and then, when the file fits, the append's
+ * write walk; a file with d_cap[i] >= rle_append_slot_bytes(C, A) cannot overflow, skips the size walk
+ * and costs what rle_append_batch_device costs.  Segmented forms: the launches of
+ * rle_append_batch_device_seg (plan, map, entry, summary, scan, write; the size form has no write
+ * launch), its workspace (rle_append_seg_workspace_bytes(n, total_new_bytes)) and its host-side
+ * returns: n == 0 is RLE_OK; a NULL required pointer (d_need among them) or workspace, or
+ * workspace_bytes below that size, is RLE_E_INVAL; a file past the tables gets RLE_STATUS_TOOLARGE
+ * (d_need[i] = 0).  No entry routes to another form: the caller picks, as above.
+ * Size and then fit when the slot may have to move or the store's limit decides (refuse, evict or
+ * relocate between the two calls); fit alone when a slot that is too small is the rare case, and
+ * d_need of the NOFIT files says what to relocate them to.
+ * Measured on one MI355X against the plain append in the same process (profiles/append_fit.json,
+ * DESIGN.md §4b): 4096 appends of 4 KiB, size 12 us against 17-22 us, fit into exact slots 21-26 us,
+ * fit into worst-case slots 17-22 us; 64 appends of 1 MiB (segmented), size 37 us against 69-92 us,
+ * fit in either kind of slot within the rounds' spread of the plain append. */
+int rle_append_size_batch_device(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                                 const uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
+                                 const uint64_t* d_new_len, uint64_t* d_need, uint32_t* d_status, uint32_t n,
+                                 void* stream);
+int rle_append_size_batch_device_seg(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                                     const uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
+                                     const uint64_t* d_new_len, uint64_t* d_need, uint32_t* d_status, uint32_t n,
+                                     uint64_t total_new_bytes, void* d_workspace, size_t workspace_bytes,
+                                     void* stream);
+int rle_append_fit_batch_device(void* d_streams, const uint64_t* d_off, uint64_t* d_len, const uint64_t* d_cap,
+                                uint64_t* d_ulen, uint64_t* d_tail, const void* d_new, const uint64_t* d_new_off,
+                                const uint64_t* d_new_len, uint64_t* d_need, uint32_t* d_status, uint32_t n,
+                                void* stream);
+int rle_append_fit_batch_device_seg(void* d_streams, const uint64_t* d_off, uint64_t* d_len, const uint64_t* d_cap,
+                                    uint64_t* d_ulen, uint64_t* d_tail, const void* d_new,
+                                    const uint64_t* d_new_off, const uint64_t* d_new_len, uint64_t* d_need,
+                                    uint32_t* d_status, uint32_t n, uint64_t total_new_bytes, void* d_workspace,
+                                    size_t workspace_bytes, void* stream);
 
 /* Diagnostic builds only (RLE_STAMPS=1, never the product library): per-segment decode cycle sums
  * over all waves: [tile wait, scan, scatter, flush reads, flush fill, flush store, flush re-zero,
