@@ -404,14 +404,29 @@ def tail_count(w: int) -> int:
     return (int(w) >> 32) & 0xF
 
 
+def _seg_defaults(n, lengths, total, ws, make_ws, device):
+    """(total, ws) of a _seg call of the tail scan or the append: total None is the sum of lengths,
+    read back from the device (which synchronises); ws None is a fresh workspace from make_ws."""
+    total = int(lengths.sum().item()) if total is None else int(total)
+    return total, ws if ws is not None else make_ws(n, total, device)
+
+
+def _default_tail(tail, d_streams, off, length, stream):
+    """The tail words of an append: the tensor given, or a fresh one filled by a scan of the streams
+    (tail_batch) first."""
+    if tail is None:
+        import torch
+        tail = torch.zeros(off.numel(), dtype=torch.int64, device=d_streams.device)
+        tail_batch(d_streams, off, length, tail, None, None, stream)
+    return tail
+
+
 def tail_batch(d_in, off, length, tail, ulen=None, status=None, stream=None):
     """rle_tail_batch_device on device tensors (uint8 streams; int64 offsets, lengths, tail words and
     decoded lengths; int32 status): the tail word t | r << 32 and the decoded length of every stream,
     reading the streams only."""
-    rc = lib().rle_tail_batch_device(_ptr(d_in), _ptr(off), _ptr(length), _ptr(tail), _ptr(ulen), _ptr(status),
-                                     off.numel(), _stream_ptr(stream))
-    if rc != RLE_OK:
-        raise RLEError(f"rle_tail_batch_device failed: {rc}")
+    _check(lib().rle_tail_batch_device(_ptr(d_in), _ptr(off), _ptr(length), _ptr(tail), _ptr(ulen), _ptr(status),
+                                       off.numel(), _stream_ptr(stream)), "rle_tail_batch_device")
 
 
 def tail_seg_workspace(n: int, total_in_bytes: int, device=None):
@@ -428,14 +443,9 @@ def tail_batch_seg(d_in, off, length, tail, ulen=None, status=None, total_in_byt
     synchronises (the sum is read back from the device): a call captured into a graph must pass
     total_in_bytes and ws."""
     n = off.numel()
-    total = int(length.sum().item()) if total_in_bytes is None else int(total_in_bytes)
-    if ws is None:
-        ws = tail_seg_workspace(n, total, d_in.device)
-    wp, wn = _ws_ptr(ws)
-    rc = lib().rle_tail_batch_device_seg(_ptr(d_in), _ptr(off), _ptr(length), _ptr(tail), _ptr(ulen), _ptr(status),
-                                         n, total, wp, wn, _stream_ptr(stream))
-    if rc != RLE_OK:
-        raise RLEError(f"rle_tail_batch_device_seg failed: {rc}")
+    total, ws = _seg_defaults(n, length, total_in_bytes, ws, tail_seg_workspace, d_in.device)
+    _check(lib().rle_tail_batch_device_seg(_ptr(d_in), _ptr(off), _ptr(length), _ptr(tail), _ptr(ulen), _ptr(status),
+                                           n, total, *_ws_ptr(ws), _stream_ptr(stream)), "rle_tail_batch_device_seg")
 
 
 def append_batch(d_streams, off, length, cap, ulen, d_new, new_off, new_len, status=None, tail=None, stream=None):
@@ -444,15 +454,10 @@ def append_batch(d_streams, off, length, cap, ulen, d_new, new_off, new_len, sta
     (may be None) and tail are updated.  tail=None: the tail words come from a scan of the streams
     first (tail_batch) into a fresh tensor.  Returns the tail tensor, to be carried into the next
     append."""
-    if tail is None:
-        import torch
-        tail = torch.zeros(off.numel(), dtype=torch.int64, device=d_streams.device)
-        tail_batch(d_streams, off, length, tail, None, None, stream)
-    rc = lib().rle_append_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen), _ptr(tail),
-                                       _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(status), off.numel(),
-                                       _stream_ptr(stream))
-    if rc != RLE_OK:
-        raise RLEError(f"rle_append_batch_device failed: {rc}")
+    tail = _default_tail(tail, d_streams, off, length, stream)
+    _check(lib().rle_append_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen), _ptr(tail),
+                                         _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(status), off.numel(),
+                                         _stream_ptr(stream)), "rle_append_batch_device")
     return tail
 
 
@@ -472,29 +477,20 @@ def append_batch_seg(d_streams, off, length, cap, ulen, d_new, new_off, new_len,
     from the device) and the default tail launches a scan into a new tensor: a call captured into a
     graph must pass total_new_bytes, workspace and tail."""
     n = off.numel()
-    if tail is None:
-        import torch
-        tail = torch.zeros(n, dtype=torch.int64, device=d_streams.device)
-        tail_batch(d_streams, off, length, tail, None, None, stream)
-    total = int(new_len.sum().item()) if total_new_bytes is None else int(total_new_bytes)
-    ws = workspace if workspace is not None else append_seg_workspace(n, total, d_streams.device)
-    wp, wn = _ws_ptr(ws)
-    rc = lib().rle_append_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen), _ptr(tail),
-                                           _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(status), n, total, wp, wn,
-                                           _stream_ptr(stream))
-    if rc != RLE_OK:
-        raise RLEError(f"rle_append_batch_device_seg failed: {rc}")
+    tail = _default_tail(tail, d_streams, off, length, stream)
+    total, ws = _seg_defaults(n, new_len, total_new_bytes, workspace, append_seg_workspace, d_streams.device)
+    _check(lib().rle_append_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen),
+                                             _ptr(tail), _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(status), n,
+                                             total, *_ws_ptr(ws), _stream_ptr(stream)), "rle_append_batch_device_seg")
     return tail
 
 
 def append_size(d_streams, off, length, tail, d_new, new_off, new_len, need, status=None, stream=None):
     """rle_append_size_batch_device: need[i] = the length append_batch would leave in length[i], and
     nothing else is written (need: int64; tail: the streams' tail words, required)."""
-    rc = lib().rle_append_size_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(tail), _ptr(d_new),
-                                            _ptr(new_off), _ptr(new_len), _ptr(need), _ptr(status), off.numel(),
-                                            _stream_ptr(stream))
-    if rc != RLE_OK:
-        raise RLEError(f"rle_append_size_batch_device failed: {rc}")
+    _check(lib().rle_append_size_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(tail), _ptr(d_new),
+                                              _ptr(new_off), _ptr(new_len), _ptr(need), _ptr(status), off.numel(),
+                                              _stream_ptr(stream)), "rle_append_size_batch_device")
     return need
 
 
@@ -503,14 +499,11 @@ def append_size_seg(d_streams, off, length, tail, d_new, new_off, new_len, need,
     """rle_append_size_batch_device_seg: append_size with several waves per file.  total_new_bytes and
     workspace as in append_batch_seg (a captured call must pass both)."""
     n = off.numel()
-    total = int(new_len.sum().item()) if total_new_bytes is None else int(total_new_bytes)
-    ws = workspace if workspace is not None else append_seg_workspace(n, total, d_new.device)
-    wp, wn = _ws_ptr(ws)
-    rc = lib().rle_append_size_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(tail), _ptr(d_new),
-                                                _ptr(new_off), _ptr(new_len), _ptr(need), _ptr(status), n, total, wp,
-                                                wn, _stream_ptr(stream))
-    if rc != RLE_OK:
-        raise RLEError(f"rle_append_size_batch_device_seg failed: {rc}")
+    total, ws = _seg_defaults(n, new_len, total_new_bytes, workspace, append_seg_workspace, d_new.device)
+    _check(lib().rle_append_size_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(tail), _ptr(d_new),
+                                                  _ptr(new_off), _ptr(new_len), _ptr(need), _ptr(status), n, total,
+                                                  *_ws_ptr(ws), _stream_ptr(stream)),
+           "rle_append_size_batch_device_seg")
     return need
 
 
@@ -519,15 +512,11 @@ def append_fit(d_streams, off, length, cap, ulen, d_new, new_off, new_len, need,
     (exact); need[i] receives that length, and a file that does not fit is refused with
     RLE_STATUS_NOFIT, untouched.  tail=None: from a scan first, as in append_batch.  Returns the tail
     tensor."""
-    if tail is None:
-        import torch
-        tail = torch.zeros(off.numel(), dtype=torch.int64, device=d_streams.device)
-        tail_batch(d_streams, off, length, tail, None, None, stream)
-    rc = lib().rle_append_fit_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen), _ptr(tail),
-                                           _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(need), _ptr(status),
-                                           off.numel(), _stream_ptr(stream))
-    if rc != RLE_OK:
-        raise RLEError(f"rle_append_fit_batch_device failed: {rc}")
+    tail = _default_tail(tail, d_streams, off, length, stream)
+    _check(lib().rle_append_fit_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen),
+                                             _ptr(tail), _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(need),
+                                             _ptr(status), off.numel(), _stream_ptr(stream)),
+           "rle_append_fit_batch_device")
     return tail
 
 
@@ -536,18 +525,12 @@ def append_fit_seg(d_streams, off, length, cap, ulen, d_new, new_off, new_len, n
     """rle_append_fit_batch_device_seg: append_fit with several waves per file.  total_new_bytes,
     workspace and tail as in append_batch_seg (a captured call must pass all three)."""
     n = off.numel()
-    if tail is None:
-        import torch
-        tail = torch.zeros(n, dtype=torch.int64, device=d_streams.device)
-        tail_batch(d_streams, off, length, tail, None, None, stream)
-    total = int(new_len.sum().item()) if total_new_bytes is None else int(total_new_bytes)
-    ws = workspace if workspace is not None else append_seg_workspace(n, total, d_streams.device)
-    wp, wn = _ws_ptr(ws)
-    rc = lib().rle_append_fit_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen),
-                                               _ptr(tail), _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(need),
-                                               _ptr(status), n, total, wp, wn, _stream_ptr(stream))
-    if rc != RLE_OK:
-        raise RLEError(f"rle_append_fit_batch_device_seg failed: {rc}")
+    tail = _default_tail(tail, d_streams, off, length, stream)
+    total, ws = _seg_defaults(n, new_len, total_new_bytes, workspace, append_seg_workspace, d_streams.device)
+    _check(lib().rle_append_fit_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(cap), _ptr(ulen),
+                                                 _ptr(tail), _ptr(d_new), _ptr(new_off), _ptr(new_len), _ptr(need),
+                                                 _ptr(status), n, total, *_ws_ptr(ws), _stream_ptr(stream)),
+           "rle_append_fit_batch_device_seg")
     return tail
 
 

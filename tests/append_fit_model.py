@@ -18,7 +18,7 @@ def need(y, word, new):
 
 
 def word_ok(y, word):
-    """The tail word describes the stream's last bytes (the check of append_kernel)."""
+    """The tail word describes the stream's last bytes (the check of app_accept)."""
     y, C = bytes(y), len(y)
     if word == 0:
         return C == 0
