@@ -2158,4 +2158,47 @@ __device__ u32 dec_serial(const uint8_t* src, u32 C, u32 U, uint64_t cap, uint8_
     return readlane(st, 0);
 }
 
+// dec_serial for a destination at any byte (the packed decode, rle_kernels.hip decode_packed_kernel;
+// cap = U): the zero fill of [dst, dst + U) takes single bytes up to the first 16-byte boundary and
+// behind the last one, where the chunk holds other files' bytes, and aligned 16-byte stores between
+// them; the token walk stores single bytes below U, as dec_serial's does.  The same status bits.
+__device__ u32 dec_serial_packed(const uint8_t* src, u32 C, u32 U, uint8_t* dst, u32 lane, uint8_t* stage,
+                                 u32 stage_bytes) {
+    for (u32 k = lane; k < stage_bytes / 16u; k += kWave)
+        reinterpret_cast<u32x4*>(stage)[k] = u32x4{0u, 0u, 0u, 0u};
+    const u32 lead = (16u - ((u32)(uintptr_t)dst & 15u)) & 15u;
+    const u32 h = lead < U ? lead : U;   // bytes below the first boundary
+    const u32 nmid = (U - h) >> 4;       // whole aligned chunks
+    const u32 t0 = h + 16u * nmid;       // the last chunk's bytes: [t0, U), fewer than 16
+    if (lane < h) dst[lane] = 0;
+    for (u32 c = lane; c < nmid; c += kWave) *reinterpret_cast<u32x4*>(dst + h + 16u * c) = u32x4{0u, 0u, 0u, 0u};
+    if (lane < U - t0) dst[t0 + lane] = 0;
+    vm_drain();
+    wave_lds_sync();
+    u32 st = RLE_STATUS_SERIAL;
+    if (lane == 0) {
+        u32 o = 0, j = 0;
+        while (j < C) {
+            if (o >= U) { st |= RLE_STATUS_OVERFLOW; break; }
+            const uint8_t v = src[j];
+            dst[o++] = v;
+            const uint8_t n1 = (j + 1u < C) ? src[j + 1u] : (uint8_t)0;
+            if (v == n1) {
+                const uint8_t dgt = (j + 2u < C) ? src[j + 2u] : (uint8_t)0;
+                const int occ = (int)(int8_t)dgt - 48;
+                const u32 ex = occ < 0 ? ~0u : (occ >= 2 ? (u32)(occ - 1) : 0u);
+                const u32 room = U - o;   // (o <= U)
+                const u32 kk = ex < room ? ex : room;
+                for (u32 i = 0; i < kk; ++i) dst[o + i] = v;
+                o += kk;
+                j += 3u;
+            } else {
+                j += 1u;
+            }
+        }
+    }
+    vm_drain();
+    return readlane(st, 0);
+}
+
 }  // namespace rle

@@ -403,6 +403,150 @@ __global__ __launch_bounds__(kDecBlock) void decode_kernel(const uint8_t* __rest
     }
 }
 
+// ================================================================ packed decode (rle_decode_packed_batch_device)
+// decode_kernel for destinations at any byte: file b writes out[out_off[b], out_off[b] + U) and no
+// other byte, with files abutting and their waves running side by side.  The tile walk is entered the
+// way dec_seg_write (rle_segmented.hip) enters a segment: the output descriptor is based at the
+// destination rounded down to 16, the walk starts at output offset head = the destination's low four
+// bits with st.head = head and token phase 0, and closes with dec_finish to head + U, so the first
+// and the last 16-byte chunk, which hold other files' bytes, are finished with byte stores (the
+// st.head branches of dec_flush, dec_tile_pr and dec_finish; head + U < 2^31).  No out_cap (cap = U)
+// and no issue order.  total (rle_readn_batch_device; else NULL): the reply's length, written by
+// readn_layout_kernel ahead of this launch: past out_cap every file is RLE_STATUS_NOFIT and nothing
+// is stored.
+template <u32 kChunks, u32 kWtMode>   // (as decode_kernel's)
+__global__ __launch_bounds__(kDecBlock) void decode_packed_kernel(const uint8_t* __restrict__ in,
+                                                                  const uint64_t* __restrict__ in_off,
+                                                                  const uint64_t* __restrict__ in_len,
+                                                                  uint8_t* __restrict__ out,
+                                                                  const uint64_t* __restrict__ out_off,
+                                                                  const uint64_t* __restrict__ out_len,
+                                                                  uint32_t* __restrict__ status, uint32_t n,
+                                                                  const uint64_t* __restrict__ total,
+                                                                  uint64_t out_cap) {
+    __shared__ __attribute__((aligned(16))) uint8_t slots_all[kDecWaves * 2u * kSlot];
+    constexpr u32 kStageB = 32u * kChunks;
+    __shared__ __attribute__((aligned(128))) uint8_t stage_all[kDecWaves * kStageB];
+    __shared__ __attribute__((aligned(16))) DecEntry tbl[256];
+    __shared__ u32x4 clut[kCompactEntries];
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    const u32 b = xcd_buffer(blockIdx.x, gridDim.x, kDecWaves, wid);
+    // the per-file words and the reply's length loaded at once (index clamped; n >= 1)
+    const u32 bi = b < n ? b : 0u;
+    const uint64_t C64 = in_len[bi], U64 = out_len[bi], ioff = in_off[bi], ooff = out_off[bi];
+    const uint64_t tot = total ? *total : 0u;
+    __builtin_amdgcn_sched_barrier(0);   // (all loads in flight before the first use, as in decode_kernel)
+    const uint8_t* src = in + ioff;
+    uint8_t* dst = out + ooff;
+    const u32 head = uniform((u32)(uintptr_t)dst & 15u);
+    uint8_t* base = dst - head;
+    u32 bad = ((uintptr_t)src & 15u) ? RLE_STATUS_MISALIGNED : 0u;
+    if (C64 > kMaxBufferBytes || U64 > kMaxBufferBytes) bad |= RLE_STATUS_TOOLARGE;
+    if (tot > out_cap) bad = RLE_STATUS_NOFIT;
+    const u32 C = (u32)C64, U = (u32)U64, E = head + U;
+    const u32x4 rsi = make_rsrc(src, (C + 15u) & ~15u);
+    const u32 ntiles = (b < n && !bad) ? ntiles_for(C) : 0u;
+    if (kChunks >= 191u) {   // (decode_kernel's issue priority by walk length)
+        if (ntiles >= 32u) __builtin_amdgcn_s_setprio(3);
+        else if (ntiles >= 8u) __builtin_amdgcn_s_setprio(2);
+        else if (ntiles >= 3u) __builtin_amdgcn_s_setprio(1);
+    }
+    uint8_t* stage = stage_all + wid * kStageB;
+    const uint8_t* slots = slots_all + wid * 2u * kSlot;
+    // decode_kernel's prologue: the first tiles' loads, then wave 0's LDS-DMA of the phase table and
+    // the compaction selectors, published by one barrier
+    walk_prime(rsi, 0u, ntiles, lane, slots);
+    if (wid == 0u) {
+        const u32x4 rt = make_rsrc(&kDecTable, (u32)sizeof(DecTable));
+        const u32 lt = uniform(lds_addr(tbl));
+        asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh
+        dma_tile(rt, 16u * lane, lt);
+        dma_tile(rt, 1024u + 16u * lane, lt + 1024u);
+        if (lane < kCompactEntries)
+            dma_tile(make_rsrc(&kCompactLut, (u32)sizeof(DecCompactLut)), 16u * lane, uniform(lds_addr(clut)));
+    }
+    for (u32 k = lane; k < kStageB / 16u; k += kWave)
+        reinterpret_cast<u32x4*>(stage)[k] = u32x4{0u, 0u, 0u, 0u};
+    if (wid == 0u) vm_drain();
+    if (kDecWaves > 1) __syncthreads();
+    else wave_lds_sync();
+
+    if (b >= n) return;
+    if (bad) {
+        if (lane == 0 && status) status[b] = bad;
+        return;
+    }
+    const u32x4 rso = make_rsrc(base, E);
+    DecState st{head, 0u, 0u, 0u, 0u, head, 0u, kWtMode == 1u, {}};
+    const DecK kc = dec_k();
+    auto tile = [&](u32 t, const uint8_t* cs, const Refill& nx) {
+        return dec_tile<true, kChunks, true>(cs, nx, t * kTileStep, C, C, E, lane, tbl, stage, base, rso, st, kc, clut);
+    };
+    const bool serial = walk_tiles(rsi, 0u, ntiles, lane, slots, tile, true);
+    u32 stat;
+    if (serial) stat = dec_serial_packed(src, C, U, dst, lane, stage, kStageB);
+    else {
+        dec_finish(st, E, lane, stage, rso, base);
+        stat = dec_tiled_status(st, E);
+    }
+    if (lane == 0 && status) status[b] = stat;
+}
+
+// ================================================================ reply layout (rle_readn_layout_device)
+// place[i] = sum over k < i of (gap[k] + ulen[k]) + gap[i] and *total = the sum over all n, in 64
+// bits: one workgroup walks n in strides of its 1024 threads with the total so far carried along.
+// Per stride: a wave scan by DPP of the 64-bit terms (both halves moved, then one 64-bit add per
+// step), the 16 wave sums exchanged through LDS (two sets, taken in turn: one barrier per stride),
+// and the next stride's terms loaded ahead of the barrier.
+constexpr u32 kLayoutBlock = 1024u, kLayoutWaves = kLayoutBlock / kWave;
+template <int kCtrl, int kRowMask = 0xf>
+__device__ __forceinline__ uint64_t dpp_add64(uint64_t x) {
+    const uint64_t y = (uint64_t)dpp<kCtrl, kRowMask>(0u, (u32)x) | ((uint64_t)dpp<kCtrl, kRowMask>(0u, (u32)(x >> 32)) << 32);
+    return x + y;
+}
+__global__ __launch_bounds__(kLayoutBlock) void readn_layout_kernel(const uint64_t* __restrict__ ulen,
+                                                                    const uint64_t* __restrict__ gap,
+                                                                    uint64_t* __restrict__ place,
+                                                                    uint64_t* __restrict__ total, uint32_t n) {
+    __shared__ uint64_t wsum[2][kLayoutWaves];
+    const u32 t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
+    uint64_t carry = 0u;
+    uint64_t g = 0u, u = 0u;
+    if (t < n) {
+        g = gap ? gap[t] : 0u;
+        u = ulen[t];
+    }
+    for (u32 i0 = 0u, k = 0u; i0 < n; i0 += kLayoutBlock, ++k) {
+        const u32 i = i0 + t;
+        const uint64_t gi = g, x = g + u;
+        g = 0u;
+        u = 0u;
+        if (i + kLayoutBlock < n) {   // (no wrap: the launcher bounds n by kMaxGrid)
+            g = gap ? gap[i + kLayoutBlock] : 0u;
+            u = ulen[i + kLayoutBlock];
+        }
+        uint64_t s = x;
+        s = dpp_add64<kRowShr1>(s);
+        s = dpp_add64<kRowShr2>(s);
+        s = dpp_add64<kRowShr4>(s);
+        s = dpp_add64<kRowShr8>(s);
+        s = dpp_add64<kRowBcast15, 0xa>(s);
+        s = dpp_add64<kRowBcast31, 0xc>(s);
+        if (lane == kWave - 1) wsum[k & 1u][wv] = s;
+        __syncthreads();
+        uint64_t before = carry, all = 0u;
+        for (u32 w = 0; w < kLayoutWaves; ++w) {
+            const uint64_t ws = wsum[k & 1u][w];
+            if (w < wv) before += ws;
+            all += ws;
+        }
+        if (i < n) place[i] = before + (s - x) + gi;
+        carry += all;
+    }
+    if (t == 0) *total = carry;
+}
+
 }  // namespace rle
 #include "rle_round.h"   // the large-batch decode in rounds (dec_round_kernel)
 namespace rle {
@@ -820,6 +964,56 @@ extern "C" int rle_decode_batch_device(const void* d_in, const uint64_t* d_in_of
                                        void* d_out, const uint64_t* d_out_off, const uint64_t* d_out_len,
                                        const uint64_t* d_out_cap, uint32_t* d_status, uint32_t n, void* stream) {
     return decode_launch(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_len, d_out_cap, d_status, n, 0u, stream);
+}
+
+namespace {
+// The packed decode's launch, shared by rle_decode_packed_batch_device (d_total NULL) and
+// rle_readn_batch_device (a segmented form would enter here too): decode_launch's staging size and
+// store policy for the same n, no issue order.
+int packed_launch(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, void* d_out,
+                  const uint64_t* d_out_off, const uint64_t* d_out_len, uint32_t* d_status, uint32_t n,
+                  const uint64_t* d_total, uint64_t out_cap, void* stream) {
+    const uint32_t pol = store_policy(n, false);
+    const bool large = n > kDecRound && kDecChunksLarge != rle::kDecChunks;
+    auto kern = large ? (pol ? rle::decode_packed_kernel<kDecChunksLarge, 1u> : rle::decode_packed_kernel<kDecChunksLarge, 2u>)
+                      : (pol ? rle::decode_packed_kernel<rle::kDecChunks, 1u> : rle::decode_packed_kernel<rle::kDecChunks, 2u>);
+    hipLaunchKernelGGL(kern, dim3(grid_for(n, rle::kDecWaves)), dim3(rle::kDecBlock), 0, (hipStream_t)stream,
+                       (const uint8_t*)d_in, d_in_off, d_in_len, (uint8_t*)d_out, d_out_off, d_out_len, d_status, n,
+                       d_total, out_cap);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+int layout_launch(const uint64_t* d_ulen, const uint64_t* d_gap, uint64_t* d_place, uint64_t* d_total, uint32_t n,
+                  void* stream) {
+    hipLaunchKernelGGL(rle::readn_layout_kernel, dim3(1), dim3(rle::kLayoutBlock), 0, (hipStream_t)stream, d_ulen,
+                       d_gap, d_place, d_total, n);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+}  // namespace
+
+extern "C" int rle_decode_packed_batch_device(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                              void* d_out, const uint64_t* d_out_off, const uint64_t* d_out_len,
+                                              uint32_t* d_status, uint32_t n, void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || n > kMaxGrid) return RLE_E_INVAL;
+    return packed_launch(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_len, d_status, n, nullptr, 0u, stream);
+}
+
+extern "C" int rle_readn_layout_device(const uint64_t* d_ulen, const uint64_t* d_gap, uint64_t* d_place,
+                                       uint64_t* d_total, uint32_t n, void* stream) {
+    if (!d_total || n > kMaxGrid) return RLE_E_INVAL;
+    if (n != 0 && (!d_ulen || !d_place)) return RLE_E_INVAL;
+    return layout_launch(d_ulen, d_gap, d_place, d_total, n, stream);   // (n == 0: *d_total = 0)
+}
+
+extern "C" int rle_readn_batch_device(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                                      const uint64_t* d_ulen, const uint64_t* d_gap, void* d_out, uint64_t out_cap,
+                                      uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t n,
+                                      void* stream) {
+    if (n == 0) return d_total ? layout_launch(d_ulen, d_gap, d_place, d_total, 0u, stream) : RLE_OK;
+    if (!d_streams || !d_off || !d_len || !d_ulen || !d_out || !d_place || !d_total || n > kMaxGrid) return RLE_E_INVAL;
+    const int rc = layout_launch(d_ulen, d_gap, d_place, d_total, n, stream);
+    if (rc != RLE_OK) return rc;
+    return packed_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total, out_cap, stream);
 }
 
 // Cooperative small-buffer kernels (rle_coop.hip): 1 if launched, 0 if the batch does not qualify.

@@ -125,6 +125,12 @@ def lib():
     L.rle_append_fit_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
     L.rle_append_fit_batch_device_seg.restype = ctypes.c_int
     L.rle_append_fit_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, sz, vp]
+    L.rle_decode_packed_batch_device.restype = ctypes.c_int
+    L.rle_decode_packed_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, vp]
+    L.rle_readn_layout_device.restype = ctypes.c_int
+    L.rle_readn_layout_device.argtypes = [vp, vp, vp, vp, u32, vp]
+    L.rle_readn_batch_device.restype = ctypes.c_int
+    L.rle_readn_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, vp]
     L.rle_tail_seg_workspace_bytes.restype = sz
     L.rle_tail_seg_workspace_bytes.argtypes = [u32, u64]
     L.rle_tail_batch_device_seg.restype = ctypes.c_int
@@ -532,6 +538,32 @@ def append_fit_seg(d_streams, off, length, cap, ulen, d_new, new_off, new_len, n
                                                  _ptr(status), n, total, *_ws_ptr(ws), _stream_ptr(stream)),
            "rle_append_fit_batch_device_seg")
     return tail
+
+
+def decode_packed(d_in, in_off, in_len, d_out, out_off, out_len, status=None, stream=None):
+    """rle_decode_packed_batch_device on device tensors: decode_batch with cap = U whose destinations
+    d_out + out_off[i] may lie at any byte; file i writes exactly out_len[i] bytes there and nothing
+    else, so files may abut."""
+    _check(lib().rle_decode_packed_batch_device(_ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out), _ptr(out_off),
+                                                _ptr(out_len), _ptr(status), in_off.numel(), _stream_ptr(stream)),
+           "rle_decode_packed_batch_device")
+
+
+def readn_layout(ulen, gap, place, total, stream=None):
+    """rle_readn_layout_device: place[i] = sum over k < i of (gap[k] + ulen[k]) + gap[i] and total[0] =
+    the sum over all files (int64 device tensors; gap may be None: no gaps), in one launch."""
+    _check(lib().rle_readn_layout_device(_ptr(ulen), _ptr(gap), _ptr(place), _ptr(total), ulen.numel(),
+                                         _stream_ptr(stream)), "rle_readn_layout_device")
+
+
+def readn_batch(d_streams, off, length, ulen, gap, d_out, place, total, status=None, out_cap=None, stream=None):
+    """rle_readn_batch_device: readn_layout, then decode_packed of the streams to d_out + place[i].
+    out_cap (default: d_out's size) is the reply's capacity: a reply longer than that leaves d_out
+    untouched, every status RLE_STATUS_NOFIT, and place / total say what it takes."""
+    cap = d_out.numel() if out_cap is None else int(out_cap)
+    _check(lib().rle_readn_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(ulen), _ptr(gap), _ptr(d_out),
+                                        cap, _ptr(place), _ptr(total), _ptr(status), off.numel(),
+                                        _stream_ptr(stream)), "rle_readn_batch_device")
 
 
 def copy_device(dst, src, nbytes, stream=None):

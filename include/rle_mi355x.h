@@ -29,7 +29,10 @@
  * rle_tail_batch_device_seg (tests/test_gpu_tail_seg_replay.py),
  * rle_append_batch_device, rle_append_batch_device_seg, rle_append_size_batch_device,
  * rle_append_size_batch_device_seg, rle_append_fit_batch_device, rle_append_fit_batch_device_seg
- * (tests/test_gpu_append_fit_replay.py) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
+ * (tests/test_gpu_append_fit_replay.py), rle_decode_packed_batch_device, rle_readn_layout_device,
+ * rle_readn_batch_device (tests/test_gpu_readn_pack_replay.py; n and out_cap are frozen, lengths, gaps,
+ * offsets and data are read again and d_place, d_total and the status words written again by each
+ * replay) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
  * (global) capture mode, and the graph replayed any number of times.  The host freezes at capture
  * what it decides itself: the kernel form (from n, the max_* hints and the cooperative mode), the
  * grid, the segment length and table sizes (from the total_* hint), every pointer including the
@@ -73,7 +76,9 @@ extern "C" {
 #define RLE_STATUS_NOTCANON    0x1000u /* tail scan / append: the stream, or the tail word given for it, is not
                                           what the encoder emits; nothing written */
 #define RLE_STATUS_NOFIT       0x2000u /* fit append: the slot is smaller than the stream the append would
-                                          leave; nothing written, d_need[i] says how much it takes */
+                                          leave; nothing written, d_need[i] says how much it takes.
+                                          rle_readn_batch_device: the reply is longer than out_cap; nothing
+                                          written, *d_total says how much it takes */
 
 /* Worst-case compressed size of U bytes (every run of length 2: 3 bytes per 2 input bytes). */
 size_t rle_max_compressed_size(size_t U);
@@ -364,6 +369,68 @@ int rle_append_fit_batch_device_seg(void* d_streams, const uint64_t* d_off, uint
                                     const uint64_t* d_new_off, const uint64_t* d_new_len, uint64_t* d_need,
                                     uint32_t* d_status, uint32_t n, uint64_t total_new_bytes, void* d_workspace,
                                     size_t workspace_bytes, void* stream);
+
+/* ---- reading stored streams into a packed reply -----------------------------------
+ * The reference's batched readers build one reply buffer, file after file: readNFilesHandler
+ * (src/filesystemApi.c:663-691) writes "%010ld%s%010ld" (path length, path, content length) and the
+ * decoded content directly behind it, then the next header, growing the buffer as it goes (:665-673);
+ * the eviction loop (src/server.c:314-323) sends its victims the same way.  Contents start at
+ * whatever byte the header ends on, and their lengths live where the tail scan and the appends keep
+ * them: on the device.  These three decode into such a reply without aligned slots, without a copy of
+ * the lengths to the host and without a gather.
+ *
+ * rle_decode_packed_batch_device: rle_decode_batch_device with d_out_cap = NULL (cap = U, the
+ * reference readers' extraAllocation = 0) and no alignment rule on d_out + d_out_off[i].  File i
+ * writes exactly the bytes [d_out_off[i], d_out_off[i] + U) of d_out, U = d_out_len[i], and no other
+ * byte: files may abut, and the up to 15 bytes in front of a destination and behind its end that
+ * share a 16-byte chunk with it are other files' (or the caller's headers) and stay as they are; the
+ * first and the last chunk of a file are written with byte stores only.  Input rules, results and
+ * status words are the decode's, word for word, with cap = U: the stream's address is 16-byte aligned,
+ * bytes at or past C read as zero; for streams the encoder never emits, RLE_STATUS_SERIAL, _OVERFLOW
+ * and _SHORT with the reference's bytes in [0, U) and the zero fill of a short stream.
+ * Refused, the file's range untouched: RLE_STATUS_MISALIGNED (the stream's address only) and
+ * RLE_STATUS_TOOLARGE (C or U past RLE_MAX_BUFFER_BYTES).  d_status may be NULL.
+ * Decided on the host before anything is launched: n == 0 is RLE_OK; a NULL d_in, d_in_off, d_in_len,
+ * d_out, d_out_off or d_out_len is RLE_E_INVAL.
+ * One wave per file, the decode's tile walk entered like a segment of rle_decode_batch_device_seg at
+ * the destination's offset in its 16-byte chunk; the store policy is the decode's for the same n.
+ * There is no issue-order sort in this form (a batch of more than 4096 files runs in index order),
+ * no cooperative form and no segmented form yet.
+ *
+ * rle_readn_layout_device: the reply's layout from the lengths on the device, in 64 bits:
+ *   d_place[i] = sum over k < i of (d_gap[k] + d_ulen[k]) + d_gap[i]      (where file i's content goes)
+ *   *d_total   = sum over all n of (d_gap[k] + d_ulen[k])                  (the reply's length)
+ * d_gap[i] is the header the caller puts in front of file i (the reference reply: 20 + strlen(path));
+ * d_gap == NULL means no gaps.  One launch of one workgroup, no workspace, no allocation and no host
+ * synchronisation.  On the host: a NULL d_total, or with n > 0 a NULL d_ulen or d_place, is
+ * RLE_E_INVAL; n == 0 writes *d_total = 0 and is RLE_OK.
+ *
+ * rle_readn_batch_device: both, in two launches: the layout into d_place and d_total, then the packed
+ * decode of stream i (d_streams + d_off[i], d_len[i] = C bytes) to d_out + d_place[i], d_ulen[i]
+ * bytes.  The decode reads *d_total: when *d_total > out_cap (the bytes d_out holds) every file gets
+ * RLE_STATUS_NOFIT and no byte of d_out is written; d_place and *d_total are written all the same, so
+ * the caller can allocate *d_total bytes and call again (the reference's realloc growth).  Otherwise
+ * results and statuses are rle_decode_packed_batch_device's.  The gap bytes are never written: the
+ * caller fills its headers before or after the call.  On the host: n == 0 is RLE_OK (and writes
+ * *d_total = 0 when d_total is given); a NULL d_streams, d_off, d_len, d_ulen, d_out, d_place or
+ * d_total is RLE_E_INVAL; d_gap and d_status may be NULL.
+ *
+ * Measured on one MI355X (profiles/readn_pack.json), rle_readn_batch_device against
+ * what a caller had to do before (d_ulen copied to the host and summed there, rle_decode_batch_device
+ * into aligned slots, one device gather into the reply): 64 files of 4 KiB 17-18 us against 43-44 us,
+ * 4096 of 4 KiB 22-26 us against 66-69 us, 64 of 64 KiB 63-96 us against 85-116 us, 4096 of 64 KiB
+ * 147-167 us against 334-345 us: faster on every shape measured.  Against rle_decode_batch_device
+ * alone (aligned slots, offsets known on the host) the packed reply costs 4-8 us more per call at
+ * 4 KiB per file and 6-15 us more at 64 KiB (the layout launch, and the byte stores at both ends of
+ * every file): a caller that can use aligned slots decodes fastest there. */
+int rle_decode_packed_batch_device(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                   void* d_out, const uint64_t* d_out_off, const uint64_t* d_out_len,
+                                   uint32_t* d_status, uint32_t n, void* stream);
+int rle_readn_layout_device(const uint64_t* d_ulen, const uint64_t* d_gap, uint64_t* d_place,
+                            uint64_t* d_total, uint32_t n, void* stream);
+int rle_readn_batch_device(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                           const uint64_t* d_ulen, const uint64_t* d_gap, void* d_out, uint64_t out_cap,
+                           uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t n, void* stream);
 
 /* Diagnostic builds only (RLE_STAMPS=1, never the product library): per-segment decode cycle sums
  * over all waves: [tile wait, scan, scatter, flush reads, flush fill, flush store, flush re-zero,
