@@ -968,8 +968,8 @@ extern "C" int rle_decode_batch_device(const void* d_in, const uint64_t* d_in_of
 
 namespace {
 // The packed decode's launch, shared by rle_decode_packed_batch_device (d_total NULL) and
-// rle_readn_batch_device (a segmented form would enter here too): decode_launch's staging size and
-// store policy for the same n, no issue order.
+// rle_readn_batch_device: decode_launch's staging size and store policy for the same n, no issue
+// order.  (The segmented form has a launcher of its own, packed_seg_launch in rle_segmented.hip.)
 int packed_launch(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, void* d_out,
                   const uint64_t* d_out_off, const uint64_t* d_out_len, uint32_t* d_status, uint32_t n,
                   const uint64_t* d_total, uint64_t out_cap, void* stream) {
@@ -982,13 +982,16 @@ int packed_launch(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_
                        d_total, out_cap);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }
-int layout_launch(const uint64_t* d_ulen, const uint64_t* d_gap, uint64_t* d_place, uint64_t* d_total, uint32_t n,
-                  void* stream) {
-    hipLaunchKernelGGL(rle::readn_layout_kernel, dim3(1), dim3(rle::kLayoutBlock), 0, (hipStream_t)stream, d_ulen,
-                       d_gap, d_place, d_total, n);
+}  // namespace
+namespace rle {
+// (declared in rle_seg_device.h: rle_readn_batch_device_seg, csrc/rle_segmented.hip, makes it too)
+int readn_layout_launch(const uint64_t* d_ulen, const uint64_t* d_gap, uint64_t* d_place, uint64_t* d_total,
+                        uint32_t n, void* stream) {
+    hipLaunchKernelGGL(readn_layout_kernel, dim3(1), dim3(kLayoutBlock), 0, (hipStream_t)stream, d_ulen, d_gap, d_place,
+                       d_total, n);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }
-}  // namespace
+}  // namespace rle
 
 extern "C" int rle_decode_packed_batch_device(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
                                               void* d_out, const uint64_t* d_out_off, const uint64_t* d_out_len,
@@ -1002,16 +1005,16 @@ extern "C" int rle_readn_layout_device(const uint64_t* d_ulen, const uint64_t* d
                                        uint64_t* d_total, uint32_t n, void* stream) {
     if (!d_total || n > kMaxGrid) return RLE_E_INVAL;
     if (n != 0 && (!d_ulen || !d_place)) return RLE_E_INVAL;
-    return layout_launch(d_ulen, d_gap, d_place, d_total, n, stream);   // (n == 0: *d_total = 0)
+    return rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, n, stream);   // (n == 0: *d_total = 0)
 }
 
 extern "C" int rle_readn_batch_device(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
                                       const uint64_t* d_ulen, const uint64_t* d_gap, void* d_out, uint64_t out_cap,
                                       uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t n,
                                       void* stream) {
-    if (n == 0) return d_total ? layout_launch(d_ulen, d_gap, d_place, d_total, 0u, stream) : RLE_OK;
+    if (n == 0) return d_total ? rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, 0u, stream) : RLE_OK;
     if (!d_streams || !d_off || !d_len || !d_ulen || !d_out || !d_place || !d_total || n > kMaxGrid) return RLE_E_INVAL;
-    const int rc = layout_launch(d_ulen, d_gap, d_place, d_total, n, stream);
+    const int rc = rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, n, stream);
     if (rc != RLE_OK) return rc;
     return packed_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total, out_cap, stream);
 }

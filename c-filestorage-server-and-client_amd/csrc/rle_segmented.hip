@@ -823,6 +823,128 @@ __global__ __launch_bounds__(kSegBlock) void dec_seg_write_kernel(const uint8_t*
     });
 }
 
+// ---------------------------------------------------------------- packed forms
+// rle_decode_packed_batch_device_seg and rle_readn_batch_device_seg: the scan and the write pass for
+// destinations at any byte.  Separate kernels over the same device functions (dec_seg_window,
+// dec_seg_fill, dec_seg_write): a flag on the two kernels above changed their scheduling, and they
+// are to stay as they were ("Segmented form").
+//
+// The scan with the packed decode's refusals: the stream's address alone is tested, cap = U; with
+// total (the read-N form: the reply's length, written by readn_layout_kernel ahead of this launch)
+// every file is RLE_STATUS_NOFIT when it passes reply_cap.  The plan stays in file-relative output
+// offsets, and dec_seg_window's "decodes past U" test on U.
+__global__ __launch_bounds__(kSegBlock) void dec_seg_scan_packed_kernel(const uint8_t* __restrict__ in,
+                                                                        const uint64_t* __restrict__ in_off,
+                                                                        const uint64_t* __restrict__ in_len,
+                                                                        const uint64_t* __restrict__ out_len,
+                                                                        uint32_t* __restrict__ status, u32 n,
+                                                                        const u32* __restrict__ seg_first, u32 maxseg,
+                                                                        u32 sb, const uint4* __restrict__ summ,
+                                                                        uint2* __restrict__ plan, u32* __restrict__ bflag,
+                                                                        const uint64_t* __restrict__ total,
+                                                                        uint64_t reply_cap) {
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 b = blockIdx.x * kSegWaves + uniform(threadIdx.x / kWave);
+    if (b >= n) return;
+    const uint64_t C64 = in_len[b], U64 = out_len[b];
+    const uint64_t tot = total ? *total : 0u;
+    const uint8_t* src = in + in_off[b];
+    const u32 s0 = seg_lo(seg_first, b), s1 = seg_hi(seg_first, b, in_len, sb);
+    u32 bad = ((uintptr_t)src & 15u) ? RLE_STATUS_MISALIGNED : 0u;
+    if (C64 > kMaxBufferBytes || U64 > kMaxBufferBytes || s1 > maxseg) bad |= RLE_STATUS_TOOLARGE;
+    if (tot > reply_cap) bad = RLE_STATUS_NOFIT;
+    if (bad) {
+        if (lane == 0) {
+            if (status) status[b] = bad;
+            bflag[b] = kFlagSkip;
+        }
+        return;
+    }
+    const u32 U = (u32)U64;
+    DecCarry c{0u, 0u, false};
+    for (u32 base = s0; base < s1; base += kWave) {
+        const u32 g = base + lane;
+        const bool valid = g < s1;
+        const uint4 sm = valid ? summ[g] : make_uint4(0u, 0u, 0u, 0u);
+        const uint2 pl = dec_seg_window(sm, valid, U, c);
+        if (valid) plan[g] = pl;
+    }
+    if (lane == 0) bflag[b] = c.serial ? kFlagSerial : 0u;
+}
+
+// The write pass based the way decode_packed_kernel (rle_kernels.hip) bases one wave's walk: per file
+// head = the destination's low four bits, base = dst - head, and the output descriptor covers
+// [base, base + head + U) (head + U < 2^31).  A segment whose scanned offset is off enters at
+// head + off: DecState.head = (head + off) & 15 and the flushed position is that offset rounded down
+// to 16 (dec_seg_write), so the file's first segment gets the packed decode's entry (st.head = head,
+// phase 0) and every later one the entry it has in an aligned slot, shifted by head.  The stream's last
+// segment closes with dec_finish to head + U, its last chunk by bytes, and takes its status from
+// dec_tiled_status against head + U.  No 16-byte store of a segment covers a byte outside that
+// segment's output (tests/readn_pack_seg_model.py).  A file the scan flagged serial is decoded by its
+// first segment's wave with dec_serial_packed: dec_serial's aligned zero fill would cover the
+// neighbours' bytes at both ends.
+template <u32 kSegDecChunks>
+__global__ __launch_bounds__(kSegBlock) void dec_seg_write_packed_kernel(const uint8_t* __restrict__ in,
+                                                                         const uint64_t* __restrict__ in_off,
+                                                                         const uint64_t* __restrict__ in_len,
+                                                                         uint8_t* __restrict__ out,
+                                                                         const uint64_t* __restrict__ out_off,
+                                                                         const uint64_t* __restrict__ out_len,
+                                                                         uint32_t* __restrict__ status, u32 n,
+                                                                         const u32* __restrict__ seg_first,
+                                                                         const u32* __restrict__ seg_buf, u32 maxseg,
+                                                                         u32 sb, const uint2* __restrict__ plan,
+                                                                         const u32* __restrict__ bflag,
+                                                                         const uint4* __restrict__ summ) {
+    __shared__ __attribute__((aligned(16))) uint8_t slots_all[kSegWaves * 2 * kSlot];
+    constexpr u32 kStage = 32u * kSegDecChunks;
+    __shared__ __attribute__((aligned(128))) uint8_t stage_all[kSegWaves * kStage];
+    __shared__ DecEntry tbl[256];
+    __shared__ u32x4 clut[kCompactEntries];   // dec_tile_fast's selectors
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    for (u32 k = threadIdx.x; k < 256u; k += kSegBlock) tbl[k] = dec_entry_from(kDecTable.e[k]);
+    for (u32 k = threadIdx.x; k < kCompactEntries; k += kSegBlock)
+        clut[k] = u32x4{kCompactLut.s[4u * k], kCompactLut.s[4u * k + 1u], kCompactLut.s[4u * k + 2u],
+                        kCompactLut.s[4u * k + 3u]};
+    uint8_t* stage = stage_all + wid * kStage;
+    const uint8_t* slots = slots_all + wid * 2 * kSlot;
+    for (u32 k = lane; k < kStage / 16u; k += kWave)
+        reinterpret_cast<u32x4*>(stage)[k] = u32x4{0u, 0u, 0u, 0u};
+    __syncthreads();
+    const SegScanned scanned{plan, bflag, summ};
+    seg_walk<true>(SegCut{seg_first, seg_buf, in_len, n, maxseg, sb}, wid, scanned, [&](const Seg& s) {
+        const u32 g = s.g, b = s.b, s0 = s.s0, nseg = s.nseg;
+        const uint2 pl = s.pl;
+        const uint4 sm = s.sm;
+        const u32 C = (u32)in_len[b], U = (u32)out_len[b];
+        const uint8_t* src = in + in_off[b];
+        uint8_t* dst = out + out_off[b];
+        if (s.flag & kFlagSerial) {   // one wave decodes the whole file exactly
+            if (g == s0) {
+                const u32 stat = dec_serial_packed(src, C, U, dst, lane, stage, kStage);
+                if (lane == 0 && status) status[b] = stat;
+            }
+            return;
+        }
+        const u32 head = uniform((u32)(uintptr_t)dst & 15u);
+        uint8_t* base = dst - head;
+        const u32 E = head + U, off = head + uniform(pl.y);
+        u32 q0, q1;
+        seg_range(g - s0, nseg, C, sb, q0, q1);
+        if (g + 1u != s0 + nseg) {   // one byte throughout: no second read
+            const u32 e = uniform(pl.x);
+            if ((uniform(sm.w) >> (11u + e)) & 1u) {
+                const u32 cnt = uniform(e == 0u ? sm.x : (e == 1u ? sm.y : sm.z));
+                dec_seg_fill(base, E, off, cnt, src[q0 + e], lane);
+                return;
+            }
+        }
+        dec_seg_write<false, kSegDecChunks>(src, base, C, E, q0, q1, uniform(pl.x), off, g + 1u == s0 + nseg, lane, slots,
+                                            stage, tbl, clut, status ? status + b : nullptr);
+    });
+}
+
 
 #if RLE_VARIANTS
 // ---------------------------------------------------------------- resident single-pass decode
@@ -1180,4 +1302,58 @@ extern "C" int rle_decode_batch_device_seg(const void* d_in, const uint64_t* d_i
                        dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len, out, d_out_off, d_out_len,
                        d_out_cap, d_status, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, sh.plan, sh.bflag, sh.summ);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+
+namespace {
+// The segmented packed decode's launches, shared by rle_decode_packed_batch_device_seg (d_total NULL)
+// and rle_readn_batch_device_seg (behind its layout launch): the segmented decode's plan, map and
+// summary, which read only the streams, then the packed scan and write; the staging choice is the
+// segmented decode's for the same maxseg.
+int packed_seg_launch(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, void* d_out,
+                      const uint64_t* d_out_off, const uint64_t* d_out_len, uint32_t* d_status, uint32_t n,
+                      const uint64_t* d_total, uint64_t out_cap, const rle::SegShape& sh, hipStream_t s) {
+    const uint8_t* in = (const uint8_t*)d_in;
+    uint8_t* out = (uint8_t*)d_out;
+    rle::seg_launch_plan_map(d_in_len, n, sh, s);
+    rle::seg_launch_dec_summary(in, d_in_off, d_in_len, n, sh, s);
+    hipLaunchKernelGGL(rle::dec_seg_scan_packed_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, in,
+                       d_in_off, d_in_len, d_out_len, d_status, n, sh.seg_first, sh.maxseg, sh.sb, sh.summ, sh.plan,
+                       sh.bflag, d_total, out_cap);
+    const bool one_round = sh.maxseg <= (uint32_t)sh.ncu * 16u;
+    hipLaunchKernelGGL(one_round ? rle::dec_seg_write_packed_kernel<rle::kSegDecChunksOne>
+                                 : rle::dec_seg_write_packed_kernel<rle::kSegDecChunksMany>,
+                       dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len, out, d_out_off, d_out_len,
+                       d_status, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, sh.plan, sh.bflag, sh.summ);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+}  // namespace
+
+extern "C" size_t rle_decode_packed_seg_workspace_bytes(uint32_t n, uint64_t total_in_bytes) {
+    return rle_seg_workspace_bytes(n, total_in_bytes);
+}
+
+extern "C" int rle_decode_packed_batch_device_seg(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                                  void* d_out, const uint64_t* d_out_off, const uint64_t* d_out_len,
+                                                  uint32_t* d_status, uint32_t n, uint64_t total_in_bytes,
+                                                  void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (n == 0) return RLE_OK;
+    if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len) return RLE_E_INVAL;
+    rle::SegShape sh;
+    if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_in_bytes, 0, &sh)) return rc;
+    return packed_seg_launch(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_len, d_status, n, nullptr, 0u, sh,
+                             (hipStream_t)stream);
+}
+
+extern "C" int rle_readn_batch_device_seg(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                                          const uint64_t* d_ulen, const uint64_t* d_gap, void* d_out, uint64_t out_cap,
+                                          uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t n,
+                                          uint64_t total_in_bytes, void* d_workspace, size_t workspace_bytes,
+                                          void* stream) {
+    if (n == 0) return d_total ? rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, 0u, stream) : RLE_OK;
+    if (!d_streams || !d_off || !d_len || !d_ulen || !d_out || !d_place || !d_total || n > (1u << 30)) return RLE_E_INVAL;   // (the layout's bound on n)
+    rle::SegShape sh;
+    if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_in_bytes, 0, &sh)) return rc;
+    if (const int rc = rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, n, stream)) return rc;
+    return packed_seg_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total, out_cap, sh,
+                             (hipStream_t)stream);
 }

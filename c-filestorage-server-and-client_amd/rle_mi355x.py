@@ -131,6 +131,12 @@ def lib():
     L.rle_readn_layout_device.argtypes = [vp, vp, vp, vp, u32, vp]
     L.rle_readn_batch_device.restype = ctypes.c_int
     L.rle_readn_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, vp]
+    L.rle_decode_packed_seg_workspace_bytes.restype = sz
+    L.rle_decode_packed_seg_workspace_bytes.argtypes = [u32, u64]
+    L.rle_decode_packed_batch_device_seg.restype = ctypes.c_int
+    L.rle_decode_packed_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, sz, vp]
+    L.rle_readn_batch_device_seg.restype = ctypes.c_int
+    L.rle_readn_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, u64, vp, sz, vp]
     L.rle_tail_seg_workspace_bytes.restype = sz
     L.rle_tail_seg_workspace_bytes.argtypes = [u32, u64]
     L.rle_tail_batch_device_seg.restype = ctypes.c_int
@@ -564,6 +570,41 @@ def readn_batch(d_streams, off, length, ulen, gap, d_out, place, total, status=N
     _check(lib().rle_readn_batch_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(ulen), _ptr(gap), _ptr(d_out),
                                         cap, _ptr(place), _ptr(total), _ptr(status), off.numel(),
                                         _stream_ptr(stream)), "rle_readn_batch_device")
+
+
+def decode_packed_seg_workspace(n: int, total_in_bytes: int, device=None):
+    """A device workspace for decode_packed_seg and readn_batch_seg (caller-owned, reusable across
+    calls on one stream)."""
+    import torch
+    nb = int(lib().rle_decode_packed_seg_workspace_bytes(n, int(total_in_bytes)))
+    return torch.empty(nb + 256, dtype=torch.uint8, device=device if device is not None else "cuda")
+
+
+def decode_packed_seg(d_in, in_off, in_len, d_out, out_off, out_len, status=None, total_in_bytes=None, ws=None,
+                      stream=None):
+    """rle_decode_packed_batch_device_seg: decode_packed with several waves per stream, for streams
+    that are large next to the batch.  total_in_bytes (>= the sum of in_len; default: that sum) sizes
+    the segment tables; ws: from decode_packed_seg_workspace (default: a fresh one).  The default
+    total_in_bytes synchronises (the sum is read back from the device): a call captured into a graph
+    must pass total_in_bytes and ws."""
+    n = in_off.numel()
+    total, ws = _seg_defaults(n, in_len, total_in_bytes, ws, decode_packed_seg_workspace, d_in.device)
+    _check(lib().rle_decode_packed_batch_device_seg(_ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out), _ptr(out_off),
+                                                    _ptr(out_len), _ptr(status), n, total, *_ws_ptr(ws),
+                                                    _stream_ptr(stream)), "rle_decode_packed_batch_device_seg")
+
+
+def readn_batch_seg(d_streams, off, length, ulen, gap, d_out, place, total, status=None, out_cap=None,
+                    total_in_bytes=None, ws=None, stream=None):
+    """rle_readn_batch_device_seg: readn_batch with several waves per stream (readn_layout, then
+    decode_packed_seg to d_out + place[i]); out_cap as in readn_batch, total_in_bytes and ws as in
+    decode_packed_seg."""
+    n = off.numel()
+    cap = d_out.numel() if out_cap is None else int(out_cap)
+    tin, ws = _seg_defaults(n, length, total_in_bytes, ws, decode_packed_seg_workspace, d_streams.device)
+    _check(lib().rle_readn_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(ulen), _ptr(gap), _ptr(d_out),
+                                            cap, _ptr(place), _ptr(total), _ptr(status), n, tin, *_ws_ptr(ws),
+                                            _stream_ptr(stream)), "rle_readn_batch_device_seg")
 
 
 def copy_device(dst, src, nbytes, stream=None):

@@ -32,7 +32,9 @@
  * (tests/test_gpu_append_fit_replay.py), rle_decode_packed_batch_device, rle_readn_layout_device,
  * rle_readn_batch_device (tests/test_gpu_readn_pack_replay.py; n and out_cap are frozen, lengths, gaps,
  * offsets and data are read again and d_place, d_total and the status words written again by each
- * replay) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
+ * replay), rle_decode_packed_batch_device_seg, rle_readn_batch_device_seg
+ * (tests/test_gpu_readn_pack_seg_replay.py; the same, with the segment length and table sizes frozen
+ * from total_in_bytes) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
  * (global) capture mode, and the graph replayed any number of times.  The host freezes at capture
  * what it decides itself: the kernel form (from n, the max_* hints and the cooperative mode), the
  * grid, the segment length and table sizes (from the total_* hint), every pointer including the
@@ -394,8 +396,8 @@ int rle_append_fit_batch_device_seg(void* d_streams, const uint64_t* d_off, uint
  * d_out, d_out_off or d_out_len is RLE_E_INVAL.
  * One wave per file, the decode's tile walk entered like a segment of rle_decode_batch_device_seg at
  * the destination's offset in its 16-byte chunk; the store policy is the decode's for the same n.
- * There is no issue-order sort in this form (a batch of more than 4096 files runs in index order),
- * no cooperative form and no segmented form yet.
+ * There is no issue-order sort in this form (a batch of more than 4096 files runs in index order)
+ * and no cooperative form; the segmented form is rle_decode_packed_batch_device_seg below.
  *
  * rle_readn_layout_device: the reply's layout from the lengths on the device, in 64 bits:
  *   d_place[i] = sum over k < i of (d_gap[k] + d_ulen[k]) + d_gap[i]      (where file i's content goes)
@@ -431,6 +433,51 @@ int rle_readn_layout_device(const uint64_t* d_ulen, const uint64_t* d_gap, uint6
 int rle_readn_batch_device(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
                            const uint64_t* d_ulen, const uint64_t* d_gap, void* d_out, uint64_t out_cap,
                            uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t n, void* stream);
+
+/* ---- segmented packed read-N: several waves per stored stream ("Segmented form")
+ * rle_decode_packed_batch_device_seg and rle_readn_batch_device_seg are rle_decode_packed_batch_device
+ * and rle_readn_batch_device for streams that are large next to the batch: each stream is cut into
+ * the segments of rle_decode_batch_device_seg (rle_seg_segment_bytes(total_in_bytes) bytes each) that
+ * separate waves decode.  Launches: plan and map (none for n == 1), the decode's summary, a scan with
+ * the packed decode's refusals, and a write pass in which every segment enters at the destination's
+ * offset in its 16-byte chunk plus its scanned output offset; the read-N form runs the layout launch
+ * of rle_readn_layout_device first, and its scan reads *d_total.  Arguments, results and status words
+ * are those of the one-wave forms, byte for byte and word for word: file i writes exactly
+ * [d_out_off[i], d_out_off[i] + U) and no other byte, files may abut at any destination phase, the
+ * stream's address is 16-byte aligned, bytes at or past C read as zero; RLE_STATUS_SERIAL, _OVERFLOW,
+ * _SHORT, _MISALIGNED, _TOOLARGE and (read-N) _NOFIT as above, the range untouched after a refusal.
+ * Plus:
+ *   total_in_bytes   >= the sum of the n stream lengths (sizes the segment tables; a stream whose
+ *                    segments do not fit gets RLE_STATUS_TOOLARGE and its range stays untouched)
+ *   d_workspace      caller-owned device memory of at least rle_decode_packed_seg_workspace_bytes(n,
+ *                    total_in_bytes) = rle_seg_workspace_bytes(n, total_in_bytes) bytes, 256-byte
+ *                    aligned, not used by another launch in flight; the form keeps no record of its own
+ * Decided on the host before anything is launched: n == 0 is RLE_OK (the read-N form then writes
+ * *d_total = 0 when d_total is given); a NULL d_in, d_in_off, d_in_len, d_out, d_out_off or d_out_len
+ * (decode), a NULL d_streams, d_off, d_len, d_ulen, d_out, d_place or d_total (read-N), a NULL
+ * d_workspace, or workspace_bytes below that size, is RLE_E_INVAL.  d_gap and d_status may be NULL.
+ * Graph capture: the rules of the other _seg entries (tests/test_gpu_readn_pack_seg_replay.py): n,
+ * out_cap, the segment length, the table sizes and every pointer are frozen at capture; lengths, gaps,
+ * offsets and data are read again, and d_place, *d_total and every status word written again, by each
+ * replay.
+ * No entry routes to another form: the caller picks.  RLEdecompressN does not use these.
+ * Use these when the reply holds files of tens of KiB and more and there are at most a few hundred of
+ * them.  Measured on one MI355X (profiles/readn_pack_seg.json),
+ * rle_readn_batch_device_seg against rle_readn_batch_device: one 1 MiB file 24-30 us against 814-1331
+ * us, 64 of them 76-128 us against 869-1382 us, one 64 KiB file 24-29 us against 58-94 us, 64 of them
+ * 31-39 us against 64-99 us; 4096 files of 4 KiB 53-64 us against 21-28 us and 4096 of 64 KiB 204-284
+ * us against 146-178 us, where the one-wave form wins.  Against rle_decode_batch_device_seg alone
+ * (aligned slots, offsets known on the host) the packed reply costs 3-10 us more per call (1.02-1.26
+ * times), whatever the file size. */
+size_t rle_decode_packed_seg_workspace_bytes(uint32_t n, uint64_t total_in_bytes);
+int rle_decode_packed_batch_device_seg(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                       void* d_out, const uint64_t* d_out_off, const uint64_t* d_out_len,
+                                       uint32_t* d_status, uint32_t n, uint64_t total_in_bytes,
+                                       void* d_workspace, size_t workspace_bytes, void* stream);
+int rle_readn_batch_device_seg(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                               const uint64_t* d_ulen, const uint64_t* d_gap, void* d_out, uint64_t out_cap,
+                               uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t n,
+                               uint64_t total_in_bytes, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Diagnostic builds only (RLE_STAMPS=1, never the product library): per-segment decode cycle sums
  * over all waves: [tile wait, scan, scatter, flush reads, flush fill, flush store, flush re-zero,
