@@ -1,6 +1,7 @@
 // rle_kernels.hip — MI355X (gfx950, CDNA4) RLE codec: the batch kernels (one wave64 per buffer)
 // and the C ABI of include/rle_mi355x.h for them.  Device building blocks: rle_device.h.
 #include "rle_device.h"
+#include "rle_reply.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -547,6 +548,122 @@ __global__ __launch_bounds__(kLayoutBlock) void readn_layout_kernel(const uint64
     if (t == 0) *total = carry;
 }
 
+// ================================================================ reply layout with headers (rle_readn_reply_device)
+// readn_layout_kernel with the gaps derived here: gap[i] = 20 + path_len[i] ("%010ld%s%010ld"), or 10
+// for every file where path_len is NULL (the READ form's "%010ld"), and `tail` more bytes in *total
+// (the terminator's ten).  The same walk, scan and 64-bit wrapping arithmetic, as a kernel of its own
+// so that readn_layout_kernel keeps its code.
+__global__ __launch_bounds__(kLayoutBlock) void readn_reply_layout_kernel(const uint64_t* __restrict__ ulen,
+                                                                          const uint64_t* __restrict__ path_len,
+                                                                          uint64_t* __restrict__ place,
+                                                                          uint64_t* __restrict__ total, uint32_t n,
+                                                                          uint32_t tail) {
+    __shared__ uint64_t wsum[2][kLayoutWaves];
+    const u32 t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
+    uint64_t carry = 0u;
+    uint64_t g = 0u, u = 0u;
+    if (t < n) {
+        g = path_len ? 20u + path_len[t] : 10u;
+        u = ulen[t];
+    }
+    for (u32 i0 = 0u, k = 0u; i0 < n; i0 += kLayoutBlock, ++k) {
+        const u32 i = i0 + t;
+        const uint64_t gi = g, x = g + u;
+        g = 0u;
+        u = 0u;
+        if (i + kLayoutBlock < n) {   // (no wrap: the launcher bounds n by kMaxGrid)
+            g = path_len ? 20u + path_len[i + kLayoutBlock] : 10u;
+            u = ulen[i + kLayoutBlock];
+        }
+        uint64_t s = x;
+        s = dpp_add64<kRowShr1>(s);
+        s = dpp_add64<kRowShr2>(s);
+        s = dpp_add64<kRowShr4>(s);
+        s = dpp_add64<kRowShr8>(s);
+        s = dpp_add64<kRowBcast15, 0xa>(s);
+        s = dpp_add64<kRowBcast31, 0xc>(s);
+        if (lane == kWave - 1) wsum[k & 1u][wv] = s;
+        __syncthreads();
+        uint64_t before = carry, all = 0u;
+        for (u32 w = 0; w < kLayoutWaves; ++w) {
+            const uint64_t ws = wsum[k & 1u][w];
+            if (w < wv) before += ws;
+            all += ws;
+        }
+        if (i < n) place[i] = before + (s - x) + gi;
+        carry += all;
+    }
+    if (t == 0) *total = carry + tail;
+}
+
+// ================================================================ reply headers (rle_readn_headers_device)
+// One wave per file writes the header in front of the file's content, [place - gap, place), with byte
+// stores only, so no store covers a byte outside that range: READN form "%010ld%s%010ld" (lanes 0..9
+// the digits of path_len, lanes 10..19 those of ulen, all lanes stride over the path bytes), READ form
+// "%010ld" (ulen).  With RLE_REPLY_END one more wave writes the terminator's ten '0' behind the last
+// file (at 0 where n == 0).  total (the reply entries; else NULL): the reply's length from the layout
+// launch: past out_cap nothing is stored.
+constexpr u32 kHdrWaves = 4u, kHdrBlock = kHdrWaves * kWave;
+__device__ __forceinline__ u32 digit5(u32 x, u32 j) {   // decimal digit j (0: the highest) of x < 10^5
+    u32 d = 0u;
+#pragma unroll
+    for (u32 k = 0u; k < 5u; ++k) {
+        const u32 q = x / 10u;
+        if (4u - k == j) d = x - q * 10u;
+        x = q;
+    }
+    return d;
+}
+// The character of "%010ld" at position k (0..9) for a wave-uniform v: the low ten decimal digits of
+// v, as two halves of five digits; 32-bit divides by constants where v < 2^32 (< 10^10).
+__device__ __forceinline__ u32 field_char(uint64_t v, u32 k) {
+    u32 hi, lo;
+    if (v >> 32) {
+        const uint64_t r = v % 10000000000ull;
+        hi = (u32)(r / 100000u);
+        lo = (u32)(r - (uint64_t)hi * 100000u);
+    } else {
+        const u32 w = (u32)v;
+        hi = w / 100000u;
+        lo = w - hi * 100000u;
+    }
+    return 0x30u + (k < 5u ? digit5(hi, k) : digit5(lo, k - 5u));
+}
+__global__ __launch_bounds__(kHdrBlock) void readn_header_kernel(const uint8_t* __restrict__ paths,
+                                                                 const uint64_t* __restrict__ path_off,
+                                                                 const uint64_t* __restrict__ path_len,
+                                                                 const uint64_t* __restrict__ ulen,
+                                                                 uint8_t* __restrict__ out,
+                                                                 const uint64_t* __restrict__ place, uint32_t form,
+                                                                 uint32_t n, const uint64_t* __restrict__ total,
+                                                                 uint64_t out_cap) {
+    const u32 lane = threadIdx.x & (kWave - 1);
+    const u32 wid = uniform(threadIdx.x / kWave);
+    const u32 i = blockIdx.x * kHdrWaves + wid;
+    const u32 items = n + ((form & RLE_REPLY_END) ? 1u : 0u);
+    if (i >= items) return;
+    if (total && *total > out_cap) return;
+    if (i == n) {   // the terminator
+        const uint64_t at = n ? place[n - 1u] + ulen[n - 1u] : 0u;
+        if (lane < 10u) out[at + lane] = 0x30u;
+        return;
+    }
+    const uint64_t U = ulen[i], p = place[i];
+    if ((form & 0xFFu) == RLE_REPLY_READ) {
+        const u32 c = field_char(U, lane < 10u ? lane : 0u);
+        if (lane < 10u) out[p - 10u + lane] = (uint8_t)c;
+        return;
+    }
+    const uint64_t L = path_len[i];
+    const uint8_t* src = paths + path_off[i];
+    uint8_t* h = out + (p - 20u - L);
+    const u32 k = lane < 10u ? lane : lane < 20u ? lane - 10u : 0u;
+    const u32 cl = field_char(L, k), cu = field_char(U, k);
+    if (lane < 10u) h[lane] = (uint8_t)cl;
+    else if (lane < 20u) h[10u + L + (lane - 10u)] = (uint8_t)cu;
+    for (uint64_t j = lane; j < L; j += kWave) h[10u + j] = src[j];
+}
+
 }  // namespace rle
 #include "rle_round.h"   // the large-batch decode in rounds (dec_round_kernel)
 namespace rle {
@@ -991,6 +1108,24 @@ int readn_layout_launch(const uint64_t* d_ulen, const uint64_t* d_gap, uint64_t*
                        d_total, n);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }
+// (declared in rle_reply.h, for rle_readn_reply_device_seg as well)
+int readn_reply_layout_launch(const uint64_t* d_ulen, const uint64_t* d_path_len, uint64_t* d_place,
+                              uint64_t* d_total, uint32_t form, uint32_t n, void* stream) {
+    hipLaunchKernelGGL(readn_reply_layout_kernel, dim3(1), dim3(kLayoutBlock), 0, (hipStream_t)stream, d_ulen,
+                       form == RLE_REPLY_READ ? nullptr : d_path_len, d_place, d_total, n,
+                       (form & RLE_REPLY_END) ? 10u : 0u);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
+int readn_header_launch(const void* d_paths, const uint64_t* d_path_off, const uint64_t* d_path_len,
+                        const uint64_t* d_ulen, void* d_out, const uint64_t* d_place, uint32_t form, uint32_t n,
+                        const uint64_t* d_total, uint64_t out_cap, void* stream) {
+    const uint32_t items = n + ((form & RLE_REPLY_END) ? 1u : 0u);   // (n <= 1 << 30)
+    if (items == 0) return RLE_OK;
+    hipLaunchKernelGGL(readn_header_kernel, dim3((items + kHdrWaves - 1u) / kHdrWaves), dim3(kHdrBlock), 0,
+                       (hipStream_t)stream, (const uint8_t*)d_paths, d_path_off, d_path_len, d_ulen, (uint8_t*)d_out,
+                       d_place, form, n, d_total, out_cap);
+    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
+}
 }  // namespace rle
 
 extern "C" int rle_decode_packed_batch_device(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
@@ -1017,6 +1152,42 @@ extern "C" int rle_readn_batch_device(const void* d_streams, const uint64_t* d_o
     const int rc = rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, n, stream);
     if (rc != RLE_OK) return rc;
     return packed_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total, out_cap, stream);
+}
+
+extern "C" size_t rle_reply_header_bytes(uint32_t form, uint64_t path_len) {
+    if (!rle::reply_form_ok(form)) return 0;
+    return form == RLE_REPLY_READ ? 10u : (size_t)(20u + path_len);
+}
+
+extern "C" int rle_readn_headers_device(const void* d_paths, const uint64_t* d_path_off, const uint64_t* d_path_len,
+                                        const uint64_t* d_ulen, void* d_out, const uint64_t* d_place, uint32_t form,
+                                        uint32_t n, void* stream) {
+    if (!rle::reply_form_ok(form) || n > kMaxGrid) return RLE_E_INVAL;
+    if (n == 0 && !(form & RLE_REPLY_END)) return RLE_OK;
+    if (!d_out) return RLE_E_INVAL;
+    if (n != 0 && (!d_ulen || !d_place)) return RLE_E_INVAL;
+    if (n != 0 && form != RLE_REPLY_READ && (!d_paths || !d_path_off || !d_path_len)) return RLE_E_INVAL;
+    return rle::readn_header_launch(d_paths, d_path_off, d_path_len, d_ulen, d_out, d_place, form, n, nullptr, 0u,
+                                    stream);
+}
+
+extern "C" int rle_readn_reply_device(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                                      const uint64_t* d_ulen, const void* d_paths, const uint64_t* d_path_off,
+                                      const uint64_t* d_path_len, void* d_out, uint64_t out_cap, uint64_t* d_place,
+                                      uint64_t* d_total, uint32_t* d_status, uint32_t form, uint32_t n,
+                                      void* stream) {
+    if (!rle::reply_form_ok(form)) return RLE_E_INVAL;
+    if (n == 0 && !(form & RLE_REPLY_END))   // (as rle_readn_batch_device: *d_total = 0 where it is given)
+        return d_total ? rle::readn_reply_layout_launch(d_ulen, d_path_len, d_place, d_total, form, 0u, stream) : RLE_OK;
+    if (!rle::reply_args_ok(d_streams, d_off, d_len, d_ulen, d_paths, d_path_off, d_path_len, d_out, d_place, d_total,
+                            form, n) || n > kMaxGrid)
+        return RLE_E_INVAL;
+    int rc = rle::readn_reply_layout_launch(d_ulen, d_path_len, d_place, d_total, form, n, stream);
+    if (rc == RLE_OK && n != 0)
+        rc = packed_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total, out_cap, stream);
+    if (rc != RLE_OK) return rc;
+    return rle::readn_header_launch(d_paths, d_path_off, d_path_len, d_ulen, d_out, d_place, form, n, d_total, out_cap,
+                                    stream);
 }
 
 // Cooperative small-buffer kernels (rle_coop.hip): 1 if launched, 0 if the batch does not qualify.

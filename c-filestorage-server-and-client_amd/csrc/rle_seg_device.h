@@ -409,5 +409,8 @@ void seg_launch_dec_summary(const uint8_t* in, const uint64_t* off, const uint64
 // decode; n is bounded by the caller (1 << 30).
 int readn_layout_launch(const uint64_t* d_ulen, const uint64_t* d_gap, uint64_t* d_place, uint64_t* d_total,
                         uint32_t n, void* stream);
+}  // namespace rle
+#include "rle_reply.h"   // the full reply's launches (rle_readn_reply_device_seg makes them too)
+namespace rle {
 inline uint32_t seg_buf_grid(uint32_t n) { return (n + kSegWaves - 1u) / kSegWaves; }   // one wave per buffer
 }  // namespace rle

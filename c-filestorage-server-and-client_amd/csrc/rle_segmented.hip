@@ -1357,3 +1357,27 @@ extern "C" int rle_readn_batch_device_seg(const void* d_streams, const uint64_t*
     return packed_seg_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total, out_cap, sh,
                              (hipStream_t)stream);
 }
+
+extern "C" int rle_readn_reply_device_seg(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                                          const uint64_t* d_ulen, const void* d_paths, const uint64_t* d_path_off,
+                                          const uint64_t* d_path_len, void* d_out, uint64_t out_cap,
+                                          uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t form,
+                                          uint32_t n, uint64_t total_in_bytes, void* d_workspace,
+                                          size_t workspace_bytes, void* stream) {
+    if (!rle::reply_form_ok(form)) return RLE_E_INVAL;
+    if (n == 0 && !(form & RLE_REPLY_END))   // (as rle_readn_batch_device_seg: *d_total = 0 where it is given)
+        return d_total ? rle::readn_reply_layout_launch(d_ulen, d_path_len, d_place, d_total, form, 0u, stream) : RLE_OK;
+    if (!rle::reply_args_ok(d_streams, d_off, d_len, d_ulen, d_paths, d_path_off, d_path_len, d_out, d_place, d_total,
+                            form, n) || n > (1u << 30))   // (the layout's bound on n)
+        return RLE_E_INVAL;
+    rle::SegShape sh;
+    if (n != 0)   // (the terminator alone decodes nothing and needs no workspace)
+        if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_in_bytes, 0, &sh)) return rc;
+    if (const int rc = rle::readn_reply_layout_launch(d_ulen, d_path_len, d_place, d_total, form, n, stream)) return rc;
+    if (n != 0)
+        if (const int rc = packed_seg_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total,
+                                             out_cap, sh, (hipStream_t)stream))
+            return rc;
+    return rle::readn_header_launch(d_paths, d_path_off, d_path_len, d_ulen, d_out, d_place, form, n, d_total, out_cap,
+                                    stream);
+}

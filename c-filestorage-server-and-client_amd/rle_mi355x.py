@@ -32,6 +32,9 @@ RLE_STATUS_NOFIT = 0x2000
 RLE_TAIL_EMPTY = 0
 RLE_MAX_BUFFER_BYTES = 0x7FFFFFF0
 RLE_LAUNCH_STATUS_FLAG = 2
+RLE_REPLY_READN = 0
+RLE_REPLY_READ = 1
+RLE_REPLY_END = 0x100
 
 _u64p = ctypes.c_void_p
 _lib = None
@@ -137,6 +140,14 @@ def lib():
     L.rle_decode_packed_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, u64, vp, sz, vp]
     L.rle_readn_batch_device_seg.restype = ctypes.c_int
     L.rle_readn_batch_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, u64, vp, sz, vp]
+    L.rle_reply_header_bytes.restype = sz
+    L.rle_reply_header_bytes.argtypes = [u32, u64]
+    L.rle_readn_headers_device.restype = ctypes.c_int
+    L.rle_readn_headers_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp]
+    L.rle_readn_reply_device.restype = ctypes.c_int
+    L.rle_readn_reply_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, u32, vp]
+    L.rle_readn_reply_device_seg.restype = ctypes.c_int
+    L.rle_readn_reply_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, u32, u64, vp, sz, vp]
     L.rle_tail_seg_workspace_bytes.restype = sz
     L.rle_tail_seg_workspace_bytes.argtypes = [u32, u64]
     L.rle_tail_batch_device_seg.restype = ctypes.c_int
@@ -605,6 +616,46 @@ def readn_batch_seg(d_streams, off, length, ulen, gap, d_out, place, total, stat
     _check(lib().rle_readn_batch_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(ulen), _ptr(gap), _ptr(d_out),
                                             cap, _ptr(place), _ptr(total), _ptr(status), n, tin, *_ws_ptr(ws),
                                             _stream_ptr(stream)), "rle_readn_batch_device_seg")
+
+
+def reply_header_bytes(form: int, path_len: int = 0) -> int:
+    """rle_reply_header_bytes: the header's length in front of a file, 20 + path_len (RLE_REPLY_READN)
+    or 10 (RLE_REPLY_READ); 0 for a bad form."""
+    return int(lib().rle_reply_header_bytes(form, int(path_len)))
+
+
+def readn_headers(d_paths, path_off, path_len, ulen, d_out, place, form=RLE_REPLY_READN, stream=None):
+    """rle_readn_headers_device: file i's header into d_out[place[i] - gap_i : place[i]] from the path
+    table (d_paths uint8, path_off / path_len int64; None in the READ form) and ulen on the device;
+    with RLE_REPLY_END the ten '0' behind the last file.  No other byte is written."""
+    _check(lib().rle_readn_headers_device(_ptr(d_paths), _ptr(path_off), _ptr(path_len), _ptr(ulen), _ptr(d_out),
+                                          _ptr(place), form, ulen.numel(), _stream_ptr(stream)),
+           "rle_readn_headers_device")
+
+
+def readn_reply(d_streams, off, length, ulen, d_paths, path_off, path_len, d_out, place, total, status=None,
+                form=RLE_REPLY_READN, out_cap=None, stream=None):
+    """rle_readn_reply_device: the whole wire reply -- the layout with the header lengths derived from
+    path_len, readn_batch's packed decode, the headers and (RLE_REPLY_END) the terminator -- on one
+    stream; total[0] bytes of d_out are the reply.  out_cap as in readn_batch."""
+    cap = d_out.numel() if out_cap is None else int(out_cap)
+    _check(lib().rle_readn_reply_device(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(ulen), _ptr(d_paths),
+                                        _ptr(path_off), _ptr(path_len), _ptr(d_out), cap, _ptr(place), _ptr(total),
+                                        _ptr(status), form, off.numel(), _stream_ptr(stream)),
+           "rle_readn_reply_device")
+
+
+def readn_reply_seg(d_streams, off, length, ulen, d_paths, path_off, path_len, d_out, place, total, status=None,
+                    form=RLE_REPLY_READN, out_cap=None, total_in_bytes=None, ws=None, stream=None):
+    """rle_readn_reply_device_seg: readn_reply over readn_batch_seg's launches; total_in_bytes and ws as
+    in decode_packed_seg."""
+    n = off.numel()
+    cap = d_out.numel() if out_cap is None else int(out_cap)
+    tin, ws = _seg_defaults(n, length, total_in_bytes, ws, decode_packed_seg_workspace, d_streams.device)
+    _check(lib().rle_readn_reply_device_seg(_ptr(d_streams), _ptr(off), _ptr(length), _ptr(ulen), _ptr(d_paths),
+                                            _ptr(path_off), _ptr(path_len), _ptr(d_out), cap, _ptr(place),
+                                            _ptr(total), _ptr(status), form, n, tin, *_ws_ptr(ws),
+                                            _stream_ptr(stream)), "rle_readn_reply_device_seg")
 
 
 def copy_device(dst, src, nbytes, stream=None):

@@ -34,7 +34,9 @@
  * offsets and data are read again and d_place, d_total and the status words written again by each
  * replay), rle_decode_packed_batch_device_seg, rle_readn_batch_device_seg
  * (tests/test_gpu_readn_pack_seg_replay.py; the same, with the segment length and table sizes frozen
- * from total_in_bytes) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
+ * from total_in_bytes), rle_readn_headers_device, rle_readn_reply_device, rle_readn_reply_device_seg
+ * (tests/test_gpu_readn_reply_replay.py; n, form and out_cap are frozen, names and lengths are read
+ * again) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
  * (global) capture mode, and the graph replayed any number of times.  The host freezes at capture
  * what it decides itself: the kernel form (from n, the max_* hints and the cooperative mode), the
  * grid, the segment length and table sizes (from the total_* hint), every pointer including the
@@ -413,7 +415,8 @@ int rle_append_fit_batch_device_seg(void* d_streams, const uint64_t* d_off, uint
  * RLE_STATUS_NOFIT and no byte of d_out is written; d_place and *d_total are written all the same, so
  * the caller can allocate *d_total bytes and call again (the reference's realloc growth).  Otherwise
  * results and statuses are rle_decode_packed_batch_device's.  The gap bytes are never written: the
- * caller fills its headers before or after the call.  On the host: n == 0 is RLE_OK (and writes
+ * caller fills its headers before or after the call (rle_readn_reply_device below writes them from
+ * device state).  On the host: n == 0 is RLE_OK (and writes
  * *d_total = 0 when d_total is given); a NULL d_streams, d_off, d_len, d_ulen, d_out, d_place or
  * d_total is RLE_E_INVAL; d_gap and d_status may be NULL.
  *
@@ -477,6 +480,93 @@ int rle_decode_packed_batch_device_seg(const void* d_in, const uint64_t* d_in_of
 int rle_readn_batch_device_seg(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
                                const uint64_t* d_ulen, const uint64_t* d_gap, void* d_out, uint64_t out_cap,
                                uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t n,
+                               uint64_t total_in_bytes, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- the whole read-N reply: headers and terminator from device state ("Headers and
+ * terminator")
+ * The entries above leave the gaps to the caller, and the second number of each header is the file's
+ * decoded length, which lives in d_ulen on the device.  These four write the wire reply itself, so
+ * that one call and one copy of *d_total bytes to the host give what the reference hands to writen;
+ * nothing is copied to the host or synchronised on the way.  What the caller still does itself: keep
+ * the path table on the device (upload it when names change), and the one D2H copy of the reply.
+ *
+ * The path table: file i's name is the d_path_len[i] bytes at d_paths + d_path_off[i], at any
+ * alignment, without a NUL; the bytes are copied as they are.
+ *
+ * form:
+ *   RLE_REPLY_READN  header "%010ld%s%010ld" (path length, path, content length), 20 + d_path_len[i]
+ *                    bytes: readNFilesHandler (src/filesystemApi.c:675-679) and the eviction loop's
+ *                    SEND_EVICTED_FILE (src/server.c:53-58)
+ *   RLE_REPLY_READ   header "%010ld" (content length), 10 bytes: READ_FILE's reply
+ *                    (src/server.c:262-264); d_paths, d_path_off and d_path_len are not read and may
+ *                    be NULL
+ *   RLE_REPLY_END    or-ed to RLE_REPLY_READN only: the reference's NO_MORE_CONTENT, the ten bytes
+ *                    "0000000000" (src/server.c:122, :285, :326), follows the last file and is
+ *                    counted in *d_total
+ * Any other bit, or RLE_REPLY_END with RLE_REPLY_READ, is RLE_E_INVAL.
+ * A field holds ten digits: of a value of 10^10 or more (a d_path_len or d_ulen no real reply has)
+ * the low ten decimal digits are written, where the reference's snprintf would write more than ten.
+ * Keeping d_path_len sane is the caller's duty; a d_ulen past RLE_MAX_BUFFER_BYTES is
+ * RLE_STATUS_TOOLARGE in the decode anyway.
+ *
+ * rle_reply_header_bytes (host only): the header's length, 20 + path_len or 10; 0 for a bad form.
+ *
+ * rle_readn_headers_device: the header writer alone, for places the caller already has (beside
+ * rle_readn_layout_device with d_gap[i] = rle_reply_header_bytes(form, d_path_len[i])).  File i's
+ * header goes to exactly [d_place[i] - gap_i, d_place[i]) of d_out and no other byte is touched: the
+ * bytes that share a 16-byte chunk with it are other files' and are written with byte stores only.
+ * With RLE_REPLY_END the terminator goes to the ten bytes at d_place[n-1] + d_ulen[n-1] (at 0 for
+ * n == 0).  One launch, one wave per file.  On the host: n == 0 without RLE_REPLY_END is RLE_OK and
+ * launches nothing; a bad form, a NULL d_out, with n > 0 a NULL d_ulen or d_place, and in the READN
+ * form with n > 0 a NULL d_paths, d_path_off or d_path_len, is RLE_E_INVAL.
+ *
+ * rle_readn_reply_device: the reply in three launches: the layout with the gaps derived on the device
+ * from d_path_len (and the terminator's ten bytes in *d_total), rle_readn_batch_device's packed
+ * decode, and the headers and the terminator.  Content bytes and status words are those of
+ * rle_readn_batch_device, word for word.  Headers are written for every file whenever the reply
+ * fits: a file whose decode is refused (RLE_STATUS_MISALIGNED, _TOOLARGE) or flagged (_SERIAL,
+ * _OVERFLOW, _SHORT) still gets its header, since its name and length are known, and its status word
+ * tells the rest.  When *d_total > out_cap every file is RLE_STATUS_NOFIT and no byte of d_out is
+ * written, neither header nor terminator; d_place and *d_total are written all the same.
+ * n == 0: without RLE_REPLY_END RLE_OK (and *d_total = 0 when d_total is given); with it the reply is
+ * the terminator alone, *d_total = 10, under the same rule for out_cap (d_out and d_total required).
+ * On the host: a bad form, a NULL d_streams, d_off, d_len, d_ulen, d_out, d_place or d_total, and in
+ * the READN form a NULL d_paths, d_path_off or d_path_len, is RLE_E_INVAL before any launch; d_status
+ * may be NULL.
+ *
+ * rle_readn_reply_device_seg: the same over the launches of rle_readn_batch_device_seg, with its
+ * total_in_bytes and its workspace (rle_decode_packed_seg_workspace_bytes(n, total_in_bytes); a NULL
+ * or short workspace is RLE_E_INVAL; none is needed for n == 0).  Reply, d_place, *d_total and status
+ * words equal the one-wave entry's.
+ *
+ * Graph capture (tests/test_gpu_readn_reply_replay.py): n, form, out_cap and every pointer (and for
+ * the _seg form the segment length, the table sizes and the workspace) are frozen; lengths, names,
+ * offsets and data are read again by each replay.
+ *
+ * Measured on one MI355X (profiles/readn_reply.json and _run2.json, two fresh runs),
+ * 49-byte headers and the terminator.  Against rle_readn_batch_device(_seg) alone the headers and
+ * their launch cost 2.1-6.3 us per call (medians; within the spreads on 22 of 32 rows), whatever the
+ * bytes decoded.  Against what a caller had to do before (d_ulen copied to the host with a
+ * synchronise, headers formatted there and copied into the gaps, then rle_readn_batch_device): 1 and
+ * 64 files of 4 KiB 17-24 us against 46-58 us, 4096 of 4 KiB 24-32 us against 227-241 us, 1 and 64
+ * files of 64 KiB 59-101 us against 93-139 us, 4096 of 64 KiB 152-185 us against 353-393 us; _seg: one
+ * 1 MiB file 24-30 us against 56-65 us, 64 of them 76-103 us against 110-146 us.  The host-header
+ * route won on no shape measured. */
+#define RLE_REPLY_READN 0u
+#define RLE_REPLY_READ  1u
+#define RLE_REPLY_END   0x100u
+size_t rle_reply_header_bytes(uint32_t form, uint64_t path_len);
+int rle_readn_headers_device(const void* d_paths, const uint64_t* d_path_off, const uint64_t* d_path_len,
+                             const uint64_t* d_ulen, void* d_out, const uint64_t* d_place, uint32_t form,
+                             uint32_t n, void* stream);
+int rle_readn_reply_device(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                           const uint64_t* d_ulen, const void* d_paths, const uint64_t* d_path_off,
+                           const uint64_t* d_path_len, void* d_out, uint64_t out_cap, uint64_t* d_place,
+                           uint64_t* d_total, uint32_t* d_status, uint32_t form, uint32_t n, void* stream);
+int rle_readn_reply_device_seg(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
+                               const uint64_t* d_ulen, const void* d_paths, const uint64_t* d_path_off,
+                               const uint64_t* d_path_len, void* d_out, uint64_t out_cap, uint64_t* d_place,
+                               uint64_t* d_total, uint32_t* d_status, uint32_t form, uint32_t n,
                                uint64_t total_in_bytes, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Diagnostic builds only (RLE_STAMPS=1, never the product library): per-segment decode cycle sums
