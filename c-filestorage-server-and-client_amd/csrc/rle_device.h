@@ -37,6 +37,7 @@ typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr u32 kWave = 64;
 constexpr u32 kMaxBufferBytes = RLE_MAX_BUFFER_BYTES;   // per-buffer limit (32-bit in-buffer offsets)
+constexpr u32 kMaxGrid = 1u << 30;   // buffers per launch: the entry points of every translation unit refuse more
 constexpr u32 kOOB = 0x80000000u;               // store offset dropped by the range check
 constexpr u32 kNotFast = 0xFFFFFFFEu;           // a fast tile path declined (the general path runs)
 

@@ -270,6 +270,39 @@ __device__ __forceinline__ u32 order_slot_local(u32 s, u32 n) {
     return (s % F) * kLocalChunk + s / F;   // slot s takes place s / F of chunk s % F
 }
 
+// Issue priority by walk length (log2 buckets of the tile count): where a SIMD holds waves of
+// unequal walks, the longest are the launch's critical path, and the short ones fill their
+// stalls: the one-round kernels (kChunks >= 191) only (every size measured within +-1 %, r5ah).
+__device__ __forceinline__ void walk_priority(u32 ntiles) {
+    if (ntiles >= 32u) __builtin_amdgcn_s_setprio(3);
+    else if (ntiles >= 8u) __builtin_amdgcn_s_setprio(2);
+    else if (ntiles >= 3u) __builtin_amdgcn_s_setprio(1);
+}
+// The prologue of decode_kernel and decode_packed_kernel, behind walk_prime.  The phase table and the
+// compaction selectors, shared by the workgroup: wave 0 LDS-DMAs them (2.3 KB) after every wave has
+// issued its first tiles' loads, waits for its own table loads (they complete in issue order, its
+// tile loads after them may still be in flight), and one barrier publishes them, normally before
+// the first tile's data has landed.  (At kernel start every wave's loads queue at once: one copy
+// per workgroup instead of per wave keeps the table traffic off the first tiles' path.)  Every wave
+// zeroes its staging (kStageB bytes) meanwhile.
+template <u32 kStageB>
+__device__ __forceinline__ void dec_prologue(u32 wid, u32 lane, DecEntry* tbl, u32x4* clut, uint8_t* stage) {
+    if (wid == 0u) {
+        const u32x4 rt = make_rsrc(&kDecTable, (u32)sizeof(DecTable));
+        const u32 lt = uniform(lds_addr(tbl));
+        asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh
+        dma_tile(rt, 16u * lane, lt);
+        dma_tile(rt, 1024u + 16u * lane, lt + 1024u);
+        if (lane < kCompactEntries)
+            dma_tile(make_rsrc(&kCompactLut, (u32)sizeof(DecCompactLut)), 16u * lane, uniform(lds_addr(clut)));
+    }
+    for (u32 k = lane; k < kStageB / 16u; k += kWave)
+        reinterpret_cast<u32x4*>(stage)[k] = u32x4{0u, 0u, 0u, 0u};
+    if (wid == 0u) vm_drain();   // (its own tile loads were issued first: both are in)
+    if (kDecWaves > 1) __syncthreads();
+    else wave_lds_sync();
+}
+
 // kChunks: staging chunks per wave (32 B each).  192 hold any tile's output in one pass; the
 // launcher takes 96 (3 KiB per wave: 7 workgroups per CU instead of 4) for batches past one
 // residency round, where the extra waves hide more latency than the two-pass staging of the
@@ -334,38 +367,12 @@ __global__ __launch_bounds__(kDecBlock) void decode_kernel(const uint8_t* __rest
     const u32x4 rsi = make_rsrc(src, (C + 15u) & ~15u);
     const u32 ntiles = (b < n && !bad && !RLE_NOWALK) ? ntiles_for(C) : 0u;
     tl_mark(b, 14u + 0u * ntiles, lane);   // (diagnostic builds: the metadata has arrived)
-    // Issue priority by walk length (log2 buckets of the tile count): where a SIMD holds waves of
-    // unequal walks, the longest are the launch's critical path, and the short ones fill their
-    // stalls: the one-round kernel (kChunks >= 191) only (every size measured within +-1 %, r5ah).
-    if (kChunks >= 191u) {
-        if (ntiles >= 32u) __builtin_amdgcn_s_setprio(3);
-        else if (ntiles >= 8u) __builtin_amdgcn_s_setprio(2);
-        else if (ntiles >= 3u) __builtin_amdgcn_s_setprio(1);
-    }
+    if (kChunks >= 191u) walk_priority(ntiles);
     uint8_t* stage = stage_all + wid * kStageB;
     const uint8_t* slots = slots_all + wid * kDepth * kSlot;
-    // The phase table and the compaction selectors, shared by the workgroup: wave 0 LDS-DMAs them
-    // (2.3 KB) after every wave has issued its first tiles' loads, waits for its own table loads
-    // (they complete in issue order, its tile loads after them may still be in flight), and one
-    // barrier publishes them, normally before the first tile's data has landed.  (At kernel start
-    // every wave's loads queue at once: one copy per workgroup instead of per wave keeps the
-    // table traffic off the first tiles' path.)
     walk_prime(rsi, 0u, ntiles, lane, slots);
     tl_mark(b, 15, lane);   // (diagnostic builds: the first tiles' loads issued)
-    if (wid == 0u) {
-        const u32x4 rt = make_rsrc(&kDecTable, (u32)sizeof(DecTable));
-        const u32 lt = uniform(lds_addr(tbl));
-        asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh
-        dma_tile(rt, 16u * lane, lt);
-        dma_tile(rt, 1024u + 16u * lane, lt + 1024u);
-        if (lane < kCompactEntries)
-            dma_tile(make_rsrc(&kCompactLut, (u32)sizeof(DecCompactLut)), 16u * lane, uniform(lds_addr(clut)));
-    }
-    for (u32 k = lane; k < kStageB / 16u; k += kWave)
-        reinterpret_cast<u32x4*>(stage)[k] = u32x4{0u, 0u, 0u, 0u};
-    if (wid == 0u) vm_drain();   // (its own tile loads were issued first: both are in)
-    if (kDecWaves > 1) __syncthreads();
-    else wave_lds_sync();
+    dec_prologue<kStageB>(wid, lane, tbl, clut, stage);
 
     if (b < n) {
         if (bad) {
@@ -448,30 +455,11 @@ __global__ __launch_bounds__(kDecBlock) void decode_packed_kernel(const uint8_t*
     const u32 C = (u32)C64, U = (u32)U64, E = head + U;
     const u32x4 rsi = make_rsrc(src, (C + 15u) & ~15u);
     const u32 ntiles = (b < n && !bad) ? ntiles_for(C) : 0u;
-    if (kChunks >= 191u) {   // (decode_kernel's issue priority by walk length)
-        if (ntiles >= 32u) __builtin_amdgcn_s_setprio(3);
-        else if (ntiles >= 8u) __builtin_amdgcn_s_setprio(2);
-        else if (ntiles >= 3u) __builtin_amdgcn_s_setprio(1);
-    }
+    if (kChunks >= 191u) walk_priority(ntiles);
     uint8_t* stage = stage_all + wid * kStageB;
     const uint8_t* slots = slots_all + wid * 2u * kSlot;
-    // decode_kernel's prologue: the first tiles' loads, then wave 0's LDS-DMA of the phase table and
-    // the compaction selectors, published by one barrier
     walk_prime(rsi, 0u, ntiles, lane, slots);
-    if (wid == 0u) {
-        const u32x4 rt = make_rsrc(&kDecTable, (u32)sizeof(DecTable));
-        const u32 lt = uniform(lds_addr(tbl));
-        asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh
-        dma_tile(rt, 16u * lane, lt);
-        dma_tile(rt, 1024u + 16u * lane, lt + 1024u);
-        if (lane < kCompactEntries)
-            dma_tile(make_rsrc(&kCompactLut, (u32)sizeof(DecCompactLut)), 16u * lane, uniform(lds_addr(clut)));
-    }
-    for (u32 k = lane; k < kStageB / 16u; k += kWave)
-        reinterpret_cast<u32x4*>(stage)[k] = u32x4{0u, 0u, 0u, 0u};
-    if (wid == 0u) vm_drain();
-    if (kDecWaves > 1) __syncthreads();
-    else wave_lds_sync();
+    dec_prologue<kStageB>(wid, lane, tbl, clut, stage);
 
     if (b >= n) return;
     if (bad) {
@@ -506,16 +494,16 @@ __device__ __forceinline__ uint64_t dpp_add64(uint64_t x) {
     const uint64_t y = (uint64_t)dpp<kCtrl, kRowMask>(0u, (u32)x) | ((uint64_t)dpp<kCtrl, kRowMask>(0u, (u32)(x >> 32)) << 32);
     return x + y;
 }
-__global__ __launch_bounds__(kLayoutBlock) void readn_layout_kernel(const uint64_t* __restrict__ ulen,
-                                                                    const uint64_t* __restrict__ gap,
-                                                                    uint64_t* __restrict__ place,
-                                                                    uint64_t* __restrict__ total, uint32_t n) {
+// gap(i): file i's gap, by the kernel's own rule.
+template <class Gap>
+__device__ __forceinline__ void readn_layout_body(const uint64_t* __restrict__ ulen, uint64_t* __restrict__ place,
+                                                  uint64_t* __restrict__ total, uint32_t n, uint32_t tail, Gap gap) {
     __shared__ uint64_t wsum[2][kLayoutWaves];
     const u32 t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
     uint64_t carry = 0u;
     uint64_t g = 0u, u = 0u;
     if (t < n) {
-        g = gap ? gap[t] : 0u;
+        g = gap(t);
         u = ulen[t];
     }
     for (u32 i0 = 0u, k = 0u; i0 < n; i0 += kLayoutBlock, ++k) {
@@ -524,55 +512,7 @@ __global__ __launch_bounds__(kLayoutBlock) void readn_layout_kernel(const uint64
         g = 0u;
         u = 0u;
         if (i + kLayoutBlock < n) {   // (no wrap: the launcher bounds n by kMaxGrid)
-            g = gap ? gap[i + kLayoutBlock] : 0u;
-            u = ulen[i + kLayoutBlock];
-        }
-        uint64_t s = x;
-        s = dpp_add64<kRowShr1>(s);
-        s = dpp_add64<kRowShr2>(s);
-        s = dpp_add64<kRowShr4>(s);
-        s = dpp_add64<kRowShr8>(s);
-        s = dpp_add64<kRowBcast15, 0xa>(s);
-        s = dpp_add64<kRowBcast31, 0xc>(s);
-        if (lane == kWave - 1) wsum[k & 1u][wv] = s;
-        __syncthreads();
-        uint64_t before = carry, all = 0u;
-        for (u32 w = 0; w < kLayoutWaves; ++w) {
-            const uint64_t ws = wsum[k & 1u][w];
-            if (w < wv) before += ws;
-            all += ws;
-        }
-        if (i < n) place[i] = before + (s - x) + gi;
-        carry += all;
-    }
-    if (t == 0) *total = carry;
-}
-
-// ================================================================ reply layout with headers (rle_readn_reply_device)
-// readn_layout_kernel with the gaps derived here: gap[i] = 20 + path_len[i] ("%010ld%s%010ld"), or 10
-// for every file where path_len is NULL (the READ form's "%010ld"), and `tail` more bytes in *total
-// (the terminator's ten).  The same walk, scan and 64-bit wrapping arithmetic, as a kernel of its own
-// so that readn_layout_kernel keeps its code.
-__global__ __launch_bounds__(kLayoutBlock) void readn_reply_layout_kernel(const uint64_t* __restrict__ ulen,
-                                                                          const uint64_t* __restrict__ path_len,
-                                                                          uint64_t* __restrict__ place,
-                                                                          uint64_t* __restrict__ total, uint32_t n,
-                                                                          uint32_t tail) {
-    __shared__ uint64_t wsum[2][kLayoutWaves];
-    const u32 t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
-    uint64_t carry = 0u;
-    uint64_t g = 0u, u = 0u;
-    if (t < n) {
-        g = path_len ? 20u + path_len[t] : 10u;
-        u = ulen[t];
-    }
-    for (u32 i0 = 0u, k = 0u; i0 < n; i0 += kLayoutBlock, ++k) {
-        const u32 i = i0 + t;
-        const uint64_t gi = g, x = g + u;
-        g = 0u;
-        u = 0u;
-        if (i + kLayoutBlock < n) {   // (no wrap: the launcher bounds n by kMaxGrid)
-            g = path_len ? 20u + path_len[i + kLayoutBlock] : 10u;
+            g = gap(i + kLayoutBlock);
             u = ulen[i + kLayoutBlock];
         }
         uint64_t s = x;
@@ -594,6 +534,24 @@ __global__ __launch_bounds__(kLayoutBlock) void readn_reply_layout_kernel(const 
         carry += all;
     }
     if (t == 0) *total = carry + tail;
+}
+// The caller's gaps (NULL: none).
+__global__ __launch_bounds__(kLayoutBlock) void readn_layout_kernel(const uint64_t* __restrict__ ulen,
+                                                                    const uint64_t* __restrict__ gap,
+                                                                    uint64_t* __restrict__ place,
+                                                                    uint64_t* __restrict__ total, uint32_t n) {
+    readn_layout_body(ulen, place, total, n, 0u, [&](u32 i) -> uint64_t { return gap ? gap[i] : 0u; });
+}
+// The full reply's (rle_readn_reply_device): the gaps are the headers', gap[i] = 20 + path_len[i]
+// ("%010ld%s%010ld"), or 10 for every file where path_len is NULL (the READ form's "%010ld"), and
+// `tail` more bytes in *total (the terminator's ten).
+__global__ __launch_bounds__(kLayoutBlock) void readn_reply_layout_kernel(const uint64_t* __restrict__ ulen,
+                                                                          const uint64_t* __restrict__ path_len,
+                                                                          uint64_t* __restrict__ place,
+                                                                          uint64_t* __restrict__ total, uint32_t n,
+                                                                          uint32_t tail) {
+    readn_layout_body(ulen, place, total, n, tail,
+                      [&](u32 i) -> uint64_t { return path_len ? 20u + path_len[i] : 10u; });
 }
 
 // ================================================================ reply headers (rle_readn_headers_device)
@@ -838,7 +796,7 @@ __global__ void selftest_kernel(uint32_t* err) {
 // ================================================================ C-ABI launchers
 namespace {
 static_assert(RLE_LAUNCH_STATUS_FLAG == rle::kLaunchFlag, "launch flag bit (rle_device.h put_status)");
-constexpr uint32_t kMaxGrid = 1u << 30;
+using rle::kMaxGrid;
 // one buffer per wave, kWaves waves per workgroup, rounded up to whole rounds of the 8 XCDs
 // (rle::xcd_buffer); the kernels have no grid-stride loop, so n is bounded (kMaxGrid)
 inline uint32_t grid_for(uint32_t n, uint32_t waves) {
@@ -1101,19 +1059,16 @@ int packed_launch(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_
 }
 }  // namespace
 namespace rle {
-// (declared in rle_seg_device.h: rle_readn_batch_device_seg, csrc/rle_segmented.hip, makes it too)
-int readn_layout_launch(const uint64_t* d_ulen, const uint64_t* d_gap, uint64_t* d_place, uint64_t* d_total,
-                        uint32_t n, void* stream) {
-    hipLaunchKernelGGL(readn_layout_kernel, dim3(1), dim3(kLayoutBlock), 0, (hipStream_t)stream, d_ulen, d_gap, d_place,
-                       d_total, n);
-    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
-}
-// (declared in rle_reply.h, for rle_readn_reply_device_seg as well)
-int readn_reply_layout_launch(const uint64_t* d_ulen, const uint64_t* d_path_len, uint64_t* d_place,
-                              uint64_t* d_total, uint32_t form, uint32_t n, void* stream) {
-    hipLaunchKernelGGL(readn_reply_layout_kernel, dim3(1), dim3(kLayoutBlock), 0, (hipStream_t)stream, d_ulen,
-                       form == RLE_REPLY_READ ? nullptr : d_path_len, d_place, d_total, n,
-                       (form & RLE_REPLY_END) ? 10u : 0u);
+// (both declared in rle_reply.h: the read-N entries of csrc/rle_segmented.hip make them too)
+int readn_layout_launch(const uint64_t* d_ulen, const uint64_t* d_gap, const ReplyHeaders* hdr, uint64_t* d_place,
+                        uint64_t* d_total, uint32_t n, void* stream) {
+    if (hdr)
+        hipLaunchKernelGGL(readn_reply_layout_kernel, dim3(1), dim3(kLayoutBlock), 0, (hipStream_t)stream, d_ulen,
+                           hdr->form == RLE_REPLY_READ ? nullptr : hdr->path_len, d_place, d_total, n,
+                           (hdr->form & RLE_REPLY_END) ? 10u : 0u);
+    else
+        hipLaunchKernelGGL(readn_layout_kernel, dim3(1), dim3(kLayoutBlock), 0, (hipStream_t)stream, d_ulen, d_gap,
+                           d_place, d_total, n);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }
 int readn_header_launch(const void* d_paths, const uint64_t* d_path_off, const uint64_t* d_path_len,
@@ -1140,18 +1095,28 @@ extern "C" int rle_readn_layout_device(const uint64_t* d_ulen, const uint64_t* d
                                        uint64_t* d_total, uint32_t n, void* stream) {
     if (!d_total || n > kMaxGrid) return RLE_E_INVAL;
     if (n != 0 && (!d_ulen || !d_place)) return RLE_E_INVAL;
-    return rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, n, stream);   // (n == 0: *d_total = 0)
+    return rle::readn_layout_launch(d_ulen, d_gap, nullptr, d_place, d_total, n, stream);   // (n == 0: *d_total = 0)
 }
+
+namespace {
+// The read-N sequence (rle_reply.h) over the one-wave packed decode: nothing to prepare.
+int readn_wave_run(const rle::ReadN& a, uint32_t* d_status) {
+    return rle::readn_run(
+        a, [] { return (int)RLE_OK; },
+        [&] {
+            return packed_launch(a.streams, a.off, a.len, a.out, a.place, a.ulen, d_status, a.n, a.total, a.out_cap,
+                                 a.stream);
+        });
+}
+}  // namespace
 
 extern "C" int rle_readn_batch_device(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
                                       const uint64_t* d_ulen, const uint64_t* d_gap, void* d_out, uint64_t out_cap,
                                       uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t n,
                                       void* stream) {
-    if (n == 0) return d_total ? rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, 0u, stream) : RLE_OK;
-    if (!d_streams || !d_off || !d_len || !d_ulen || !d_out || !d_place || !d_total || n > kMaxGrid) return RLE_E_INVAL;
-    const int rc = rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, n, stream);
-    if (rc != RLE_OK) return rc;
-    return packed_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total, out_cap, stream);
+    return readn_wave_run(rle::ReadN{d_streams, d_off, d_len, d_ulen, d_gap, d_out, out_cap, d_place, d_total, n, nullptr,
+                                     stream},
+                          d_status);
 }
 
 extern "C" size_t rle_reply_header_bytes(uint32_t form, uint64_t path_len) {
@@ -1176,18 +1141,10 @@ extern "C" int rle_readn_reply_device(const void* d_streams, const uint64_t* d_o
                                       const uint64_t* d_path_len, void* d_out, uint64_t out_cap, uint64_t* d_place,
                                       uint64_t* d_total, uint32_t* d_status, uint32_t form, uint32_t n,
                                       void* stream) {
-    if (!rle::reply_form_ok(form)) return RLE_E_INVAL;
-    if (n == 0 && !(form & RLE_REPLY_END))   // (as rle_readn_batch_device: *d_total = 0 where it is given)
-        return d_total ? rle::readn_reply_layout_launch(d_ulen, d_path_len, d_place, d_total, form, 0u, stream) : RLE_OK;
-    if (!rle::reply_args_ok(d_streams, d_off, d_len, d_ulen, d_paths, d_path_off, d_path_len, d_out, d_place, d_total,
-                            form, n) || n > kMaxGrid)
-        return RLE_E_INVAL;
-    int rc = rle::readn_reply_layout_launch(d_ulen, d_path_len, d_place, d_total, form, n, stream);
-    if (rc == RLE_OK && n != 0)
-        rc = packed_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total, out_cap, stream);
-    if (rc != RLE_OK) return rc;
-    return rle::readn_header_launch(d_paths, d_path_off, d_path_len, d_ulen, d_out, d_place, form, n, d_total, out_cap,
-                                    stream);
+    const rle::ReplyHeaders hdr{d_paths, d_path_off, d_path_len, form};
+    return readn_wave_run(rle::ReadN{d_streams, d_off, d_len, d_ulen, nullptr, d_out, out_cap, d_place, d_total, n, &hdr,
+                                     stream},
+                          d_status);
 }
 
 // Cooperative small-buffer kernels (rle_coop.hip): 1 if launched, 0 if the batch does not qualify.

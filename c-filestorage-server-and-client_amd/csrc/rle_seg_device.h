@@ -404,13 +404,5 @@ void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hi
 // tail scan (csrc/rle_fileops.hip) reads the same words.
 void seg_launch_dec_summary(const uint8_t* in, const uint64_t* off, const uint64_t* len, uint32_t n,
                             const SegShape& sh, hipStream_t s);
-// The reply layout's launch (readn_layout_kernel, csrc/rle_kernels.hip) into d_place and *d_total, which
-// rle_readn_batch_device_seg makes ahead of its scan as rle_readn_batch_device does ahead of its
-// decode; n is bounded by the caller (1 << 30).
-int readn_layout_launch(const uint64_t* d_ulen, const uint64_t* d_gap, uint64_t* d_place, uint64_t* d_total,
-                        uint32_t n, void* stream);
-}  // namespace rle
-#include "rle_reply.h"   // the full reply's launches (rle_readn_reply_device_seg makes them too)
-namespace rle {
 inline uint32_t seg_buf_grid(uint32_t n) { return (n + kSegWaves - 1u) / kSegWaves; }   // one wave per buffer
 }  // namespace rle

@@ -23,6 +23,7 @@
 // The segment cut and the encode's per-segment device code (summary, scan window, writers) live in
 // rle_seg_device.h, which the segmented append (csrc/rle_fileops.hip) builds on as well.
 #include "rle_seg_device.h"
+#include "rle_reply.h"   // the read-N entries' sequence (rle_readn_batch_device_seg, rle_readn_reply_device_seg)
 
 namespace rle {
 
@@ -684,29 +685,33 @@ __device__ __forceinline__ uint2 dec_seg_window(uint4 sm, bool valid, u32 U, Dec
     return r;
 }
 
-// one wave per buffer: entry phase and output offset of every segment; serial when the taken
-// path declines anywhere or decodes past U
-__global__ __launch_bounds__(kSegBlock) void dec_seg_scan_kernel(const uint8_t* __restrict__ in,
-                                                                 const uint64_t* __restrict__ in_off,
-                                                                 const uint64_t* __restrict__ in_len,
-                                                                 uint8_t* __restrict__ out,
-                                                                 const uint64_t* __restrict__ out_off,
-                                                                 const uint64_t* __restrict__ out_len,
-                                                                 const uint64_t* __restrict__ out_cap,
-                                                                 uint32_t* __restrict__ status, u32 n,
-                                                                 const u32* __restrict__ seg_first, u32 maxseg, u32 sb,
-                                                                 const uint4* __restrict__ summ, uint2* __restrict__ plan,
-                                                                 u32* __restrict__ bflag) {
+// The scan, one wave per buffer: entry phase and output offset of every segment; serial when the
+// taken path declines anywhere or decodes past U.  The aligned and the packed form (kPacked:
+// rle_decode_packed_batch_device_seg, rle_readn_batch_device_seg, destinations at any byte) differ in
+// what they refuse.  Aligned: a stream or a destination off 16 bytes, or out_cap below U.  Packed: the
+// stream's address alone is tested, cap = U; with total (the read-N form: the reply's length, written
+// by the layout launch ahead of this one) every file is RLE_STATUS_NOFIT when it passes reply_cap.
+// The plan is in file-relative output offsets, and dec_seg_window's "decodes past U" test on U, in
+// both.
+template <bool kPacked>
+__device__ __forceinline__ void dec_seg_scan_body(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
+                                                  uint8_t* out, const uint64_t* out_off, const uint64_t* out_len,
+                                                  const uint64_t* out_cap, uint32_t* status, u32 n,
+                                                  const u32* seg_first, u32 maxseg, u32 sb, const uint4* summ,
+                                                  uint2* plan, u32* bflag, const uint64_t* total,
+                                                  uint64_t reply_cap) {
     const u32 lane = threadIdx.x & (kWave - 1);
     const u32 b = blockIdx.x * kSegWaves + uniform(threadIdx.x / kWave);
     if (b >= n) return;
     const uint64_t C64 = in_len[b], U64 = out_len[b];
-    const uint64_t cap = out_cap ? out_cap[b] : U64;
+    const uint64_t cap = !kPacked && out_cap ? out_cap[b] : U64;
+    const uint64_t tot = kPacked && total ? *total : 0u;
     const uint8_t* src = in + in_off[b];
-    uint8_t* dst = out + out_off[b];
+    const uintptr_t dst = kPacked ? 0u : (uintptr_t)(out + out_off[b]);
     const u32 s0 = seg_lo(seg_first, b), s1 = seg_hi(seg_first, b, in_len, sb);
-    u32 bad = ((((uintptr_t)src | (uintptr_t)dst) & 15u) || cap < U64) ? RLE_STATUS_MISALIGNED : 0u;
+    u32 bad = ((((uintptr_t)src | dst) & 15u) || cap < U64) ? RLE_STATUS_MISALIGNED : 0u;
     if (C64 > kMaxBufferBytes || U64 > kMaxBufferBytes || s1 > maxseg) bad |= RLE_STATUS_TOOLARGE;
+    if (kPacked && tot > reply_cap) bad = RLE_STATUS_NOFIT;
     if (bad) {
         if (lane == 0) {
             if (status) status[b] = bad;
@@ -724,6 +729,33 @@ __global__ __launch_bounds__(kSegBlock) void dec_seg_scan_kernel(const uint8_t* 
         if (valid) plan[g] = pl;
     }
     if (lane == 0) bflag[b] = c.serial ? kFlagSerial : 0u;
+}
+__global__ __launch_bounds__(kSegBlock) void dec_seg_scan_kernel(const uint8_t* __restrict__ in,
+                                                                 const uint64_t* __restrict__ in_off,
+                                                                 const uint64_t* __restrict__ in_len,
+                                                                 uint8_t* __restrict__ out,
+                                                                 const uint64_t* __restrict__ out_off,
+                                                                 const uint64_t* __restrict__ out_len,
+                                                                 const uint64_t* __restrict__ out_cap,
+                                                                 uint32_t* __restrict__ status, u32 n,
+                                                                 const u32* __restrict__ seg_first, u32 maxseg, u32 sb,
+                                                                 const uint4* __restrict__ summ, uint2* __restrict__ plan,
+                                                                 u32* __restrict__ bflag) {
+    dec_seg_scan_body<false>(in, in_off, in_len, out, out_off, out_len, out_cap, status, n, seg_first, maxseg, sb, summ,
+                             plan, bflag, nullptr, 0u);
+}
+__global__ __launch_bounds__(kSegBlock) void dec_seg_scan_packed_kernel(const uint8_t* __restrict__ in,
+                                                                        const uint64_t* __restrict__ in_off,
+                                                                        const uint64_t* __restrict__ in_len,
+                                                                        const uint64_t* __restrict__ out_len,
+                                                                        uint32_t* __restrict__ status, u32 n,
+                                                                        const u32* __restrict__ seg_first, u32 maxseg,
+                                                                        u32 sb, const uint4* __restrict__ summ,
+                                                                        uint2* __restrict__ plan, u32* __restrict__ bflag,
+                                                                        const uint64_t* __restrict__ total,
+                                                                        uint64_t reply_cap) {
+    dec_seg_scan_body<true>(in, in_off, in_len, nullptr, nullptr, out_len, nullptr, status, n, seg_first, maxseg, sb,
+                            summ, plan, bflag, total, reply_cap);
 }
 
 // A segment whose tokens all carry one byte v (summary bit 11 + e; never a stream's last segment,
@@ -823,55 +855,11 @@ __global__ __launch_bounds__(kSegBlock) void dec_seg_write_kernel(const uint8_t*
     });
 }
 
-// ---------------------------------------------------------------- packed forms
-// rle_decode_packed_batch_device_seg and rle_readn_batch_device_seg: the scan and the write pass for
-// destinations at any byte.  Separate kernels over the same device functions (dec_seg_window,
-// dec_seg_fill, dec_seg_write): a flag on the two kernels above changed their scheduling, and they
-// are to stay as they were ("Segmented form").
-//
-// The scan with the packed decode's refusals: the stream's address alone is tested, cap = U; with
-// total (the read-N form: the reply's length, written by readn_layout_kernel ahead of this launch)
-// every file is RLE_STATUS_NOFIT when it passes reply_cap.  The plan stays in file-relative output
-// offsets, and dec_seg_window's "decodes past U" test on U.
-__global__ __launch_bounds__(kSegBlock) void dec_seg_scan_packed_kernel(const uint8_t* __restrict__ in,
-                                                                        const uint64_t* __restrict__ in_off,
-                                                                        const uint64_t* __restrict__ in_len,
-                                                                        const uint64_t* __restrict__ out_len,
-                                                                        uint32_t* __restrict__ status, u32 n,
-                                                                        const u32* __restrict__ seg_first, u32 maxseg,
-                                                                        u32 sb, const uint4* __restrict__ summ,
-                                                                        uint2* __restrict__ plan, u32* __restrict__ bflag,
-                                                                        const uint64_t* __restrict__ total,
-                                                                        uint64_t reply_cap) {
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 b = blockIdx.x * kSegWaves + uniform(threadIdx.x / kWave);
-    if (b >= n) return;
-    const uint64_t C64 = in_len[b], U64 = out_len[b];
-    const uint64_t tot = total ? *total : 0u;
-    const uint8_t* src = in + in_off[b];
-    const u32 s0 = seg_lo(seg_first, b), s1 = seg_hi(seg_first, b, in_len, sb);
-    u32 bad = ((uintptr_t)src & 15u) ? RLE_STATUS_MISALIGNED : 0u;
-    if (C64 > kMaxBufferBytes || U64 > kMaxBufferBytes || s1 > maxseg) bad |= RLE_STATUS_TOOLARGE;
-    if (tot > reply_cap) bad = RLE_STATUS_NOFIT;
-    if (bad) {
-        if (lane == 0) {
-            if (status) status[b] = bad;
-            bflag[b] = kFlagSkip;
-        }
-        return;
-    }
-    const u32 U = (u32)U64;
-    DecCarry c{0u, 0u, false};
-    for (u32 base = s0; base < s1; base += kWave) {
-        const u32 g = base + lane;
-        const bool valid = g < s1;
-        const uint4 sm = valid ? summ[g] : make_uint4(0u, 0u, 0u, 0u);
-        const uint2 pl = dec_seg_window(sm, valid, U, c);
-        if (valid) plan[g] = pl;
-    }
-    if (lane == 0) bflag[b] = c.serial ? kFlagSerial : 0u;
-}
-
+// The packed write pass (rle_decode_packed_batch_device_seg, rle_readn_batch_device_seg: destinations
+// at any byte) is a kernel of its own over the same device functions (dec_seg_fill, dec_seg_write).
+// One body for both write passes was measured and not kept: with it one aligned cell, 1 x 64 KiB
+// runs50, was slower in 2 of 8 passes where no control cell was in more than 1, and
+// dec_seg_write_kernel is what the benchmark runs (profiles/readn_fold_ab.md).
 // The write pass based the way decode_packed_kernel (rle_kernels.hip) bases one wave's walk: per file
 // head = the destination's low four bits, base = dst - head, and the output descriptor covers
 // [base, base + head + U) (head + U < 2^31).  A segment whose scanned offset is off enters at
@@ -1326,6 +1314,18 @@ int packed_seg_launch(const void* d_in, const uint64_t* d_in_off, const uint64_t
                        d_status, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, sh.plan, sh.bflag, sh.summ);
     return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
 }
+// The read-N sequence (rle_reply.h) over the segmented launches: the workspace check ahead of the
+// layout launch, and packed_seg_launch into the places it wrote.
+int readn_seg_run(const rle::ReadN& a, uint32_t* d_status, uint64_t total_in_bytes, void* d_workspace,
+                  size_t workspace_bytes) {
+    rle::SegShape sh;
+    return rle::readn_run(
+        a, [&] { return rle::seg_prologue(d_workspace, workspace_bytes, a.n, total_in_bytes, 0, &sh); },
+        [&] {
+            return packed_seg_launch(a.streams, a.off, a.len, a.out, a.place, a.ulen, d_status, a.n, a.total, a.out_cap,
+                                     sh, (hipStream_t)a.stream);
+        });
+}
 }  // namespace
 
 extern "C" size_t rle_decode_packed_seg_workspace_bytes(uint32_t n, uint64_t total_in_bytes) {
@@ -1349,13 +1349,9 @@ extern "C" int rle_readn_batch_device_seg(const void* d_streams, const uint64_t*
                                           uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t n,
                                           uint64_t total_in_bytes, void* d_workspace, size_t workspace_bytes,
                                           void* stream) {
-    if (n == 0) return d_total ? rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, 0u, stream) : RLE_OK;
-    if (!d_streams || !d_off || !d_len || !d_ulen || !d_out || !d_place || !d_total || n > (1u << 30)) return RLE_E_INVAL;   // (the layout's bound on n)
-    rle::SegShape sh;
-    if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_in_bytes, 0, &sh)) return rc;
-    if (const int rc = rle::readn_layout_launch(d_ulen, d_gap, d_place, d_total, n, stream)) return rc;
-    return packed_seg_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total, out_cap, sh,
-                             (hipStream_t)stream);
+    return readn_seg_run(rle::ReadN{d_streams, d_off, d_len, d_ulen, d_gap, d_out, out_cap, d_place, d_total, n, nullptr,
+                                    stream},
+                         d_status, total_in_bytes, d_workspace, workspace_bytes);
 }
 
 extern "C" int rle_readn_reply_device_seg(const void* d_streams, const uint64_t* d_off, const uint64_t* d_len,
@@ -1364,20 +1360,8 @@ extern "C" int rle_readn_reply_device_seg(const void* d_streams, const uint64_t*
                                           uint64_t* d_place, uint64_t* d_total, uint32_t* d_status, uint32_t form,
                                           uint32_t n, uint64_t total_in_bytes, void* d_workspace,
                                           size_t workspace_bytes, void* stream) {
-    if (!rle::reply_form_ok(form)) return RLE_E_INVAL;
-    if (n == 0 && !(form & RLE_REPLY_END))   // (as rle_readn_batch_device_seg: *d_total = 0 where it is given)
-        return d_total ? rle::readn_reply_layout_launch(d_ulen, d_path_len, d_place, d_total, form, 0u, stream) : RLE_OK;
-    if (!rle::reply_args_ok(d_streams, d_off, d_len, d_ulen, d_paths, d_path_off, d_path_len, d_out, d_place, d_total,
-                            form, n) || n > (1u << 30))   // (the layout's bound on n)
-        return RLE_E_INVAL;
-    rle::SegShape sh;
-    if (n != 0)   // (the terminator alone decodes nothing and needs no workspace)
-        if (const int rc = rle::seg_prologue(d_workspace, workspace_bytes, n, total_in_bytes, 0, &sh)) return rc;
-    if (const int rc = rle::readn_reply_layout_launch(d_ulen, d_path_len, d_place, d_total, form, n, stream)) return rc;
-    if (n != 0)
-        if (const int rc = packed_seg_launch(d_streams, d_off, d_len, d_out, d_place, d_ulen, d_status, n, d_total,
-                                             out_cap, sh, (hipStream_t)stream))
-            return rc;
-    return rle::readn_header_launch(d_paths, d_path_off, d_path_len, d_ulen, d_out, d_place, form, n, d_total, out_cap,
-                                    stream);
+    const rle::ReplyHeaders hdr{d_paths, d_path_off, d_path_len, form};
+    return readn_seg_run(rle::ReadN{d_streams, d_off, d_len, d_ulen, nullptr, d_out, out_cap, d_place, d_total, n, &hdr,
+                                    stream},
+                         d_status, total_in_bytes, d_workspace, workspace_bytes);
 }

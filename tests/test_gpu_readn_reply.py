@@ -99,6 +99,24 @@ def test_read_form_one_file():
     assert got[:10].tobytes() == b"%010d" % len(f.contents[0])
 
 
+def tiny_contents(n):
+    """n files of 0..3 bytes, every length among any four neighbours."""
+    return [bytes(0x61 + (i + k) % 26 for k in range((i + i // 4) % 4)) for i in range(n)]
+
+
+@pytest.mark.parametrize("n", [1023, 1024, 1025, 2049])
+def test_read_form_past_one_stride(n):
+    """The READ form's gaps (ten per file, no path lengths read) at the edges of the layout's stride of
+    1024 files and two strides on: reply, place and total are the model's, byte for byte."""
+    contents = tiny_contents(n)
+    lens = np.array([len(c) for c in contents])
+    assert set(lens[:4]) == {0, 1, 2, 3}
+    f = G.Files(G.names(n), contents)
+    _, place, total = f.want(RM.READ)   # (the model's figures, against the closed form)
+    assert total == 10 * n + lens.sum() and place == list(10 * np.arange(1, n + 1) + np.cumsum(lens) - lens)
+    f.check(RM.READ)
+
+
 def test_no_files():
     """n == 0: with the terminator the reply is the ten '0' (or NOFIT's nothing, under 10 bytes of
     capacity); without it *d_total = 0 and nothing is written."""
