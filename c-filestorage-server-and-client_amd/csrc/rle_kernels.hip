@@ -494,17 +494,18 @@ __device__ __forceinline__ uint64_t dpp_add64(uint64_t x) {
     const uint64_t y = (uint64_t)dpp<kCtrl, kRowMask>(0u, (u32)x) | ((uint64_t)dpp<kCtrl, kRowMask>(0u, (u32)(x >> 32)) << 32);
     return x + y;
 }
-// gap(i): file i's gap, by the kernel's own rule.
-template <class Gap>
-__device__ __forceinline__ void readn_layout_body(const uint64_t* __restrict__ ulen, uint64_t* __restrict__ place,
-                                                  uint64_t* __restrict__ total, uint32_t n, uint32_t tail, Gap gap) {
+// ulen(i), gap(i): file i's length and gap, by the kernel's own rule, each asked once per file; the
+// sums start at base (the read-N replies: 0; rle_relocate_layout_device: dst_base, rle_relocate.h).
+template <class Len, class Gap>
+__device__ __forceinline__ void readn_layout_body(Len ulen, uint64_t* __restrict__ place, uint64_t* __restrict__ total,
+                                                  uint32_t n, uint64_t base, uint32_t tail, Gap gap) {
     __shared__ uint64_t wsum[2][kLayoutWaves];
     const u32 t = threadIdx.x, lane = t & (kWave - 1), wv = t / kWave;
-    uint64_t carry = 0u;
+    uint64_t carry = base;
     uint64_t g = 0u, u = 0u;
     if (t < n) {
         g = gap(t);
-        u = ulen[t];
+        u = ulen(t);
     }
     for (u32 i0 = 0u, k = 0u; i0 < n; i0 += kLayoutBlock, ++k) {
         const u32 i = i0 + t;
@@ -513,7 +514,7 @@ __device__ __forceinline__ void readn_layout_body(const uint64_t* __restrict__ u
         u = 0u;
         if (i + kLayoutBlock < n) {   // (no wrap: the launcher bounds n by kMaxGrid)
             g = gap(i + kLayoutBlock);
-            u = ulen[i + kLayoutBlock];
+            u = ulen(i + kLayoutBlock);
         }
         uint64_t s = x;
         s = dpp_add64<kRowShr1>(s);
@@ -540,7 +541,8 @@ __global__ __launch_bounds__(kLayoutBlock) void readn_layout_kernel(const uint64
                                                                     const uint64_t* __restrict__ gap,
                                                                     uint64_t* __restrict__ place,
                                                                     uint64_t* __restrict__ total, uint32_t n) {
-    readn_layout_body(ulen, place, total, n, 0u, [&](u32 i) -> uint64_t { return gap ? gap[i] : 0u; });
+    readn_layout_body([&](u32 i) -> uint64_t { return ulen[i]; }, place, total, n, 0u, 0u,
+                      [&](u32 i) -> uint64_t { return gap ? gap[i] : 0u; });
 }
 // The full reply's (rle_readn_reply_device): the gaps are the headers', gap[i] = 20 + path_len[i]
 // ("%010ld%s%010ld"), or 10 for every file where path_len is NULL (the READ form's "%010ld"), and
@@ -550,7 +552,7 @@ __global__ __launch_bounds__(kLayoutBlock) void readn_reply_layout_kernel(const 
                                                                           uint64_t* __restrict__ place,
                                                                           uint64_t* __restrict__ total, uint32_t n,
                                                                           uint32_t tail) {
-    readn_layout_body(ulen, place, total, n, tail,
+    readn_layout_body([&](u32 i) -> uint64_t { return ulen[i]; }, place, total, n, 0u, tail,
                       [&](u32 i) -> uint64_t { return path_len ? 20u + path_len[i] : 10u; });
 }
 
@@ -1385,3 +1387,6 @@ extern "C" int rle_mi355x_device_count(void) {
 }
 
 extern "C" const char* rle_mi355x_version(void) { return "rle_mi355x 0.3 (gfx950, wave-per-buffer tiled codec)"; }
+
+// ================================================================ relocating stored streams
+#include "rle_relocate.h"

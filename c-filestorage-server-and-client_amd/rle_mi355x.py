@@ -148,6 +148,12 @@ def lib():
     L.rle_readn_reply_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, u32, vp]
     L.rle_readn_reply_device_seg.restype = ctypes.c_int
     L.rle_readn_reply_device_seg.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, u32, u32, u64, vp, sz, vp]
+    L.rle_relocate_span_bytes.restype = u64
+    L.rle_relocate_span_bytes.argtypes = [u64]
+    L.rle_relocate_layout_device.restype = ctypes.c_int
+    L.rle_relocate_layout_device.argtypes = [vp, vp, vp, u64, vp, vp, vp, u32, vp]
+    L.rle_relocate_batch_device.restype = ctypes.c_int
+    L.rle_relocate_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, vp, vp, vp, vp, u32, vp]
     L.rle_tail_seg_workspace_bytes.restype = sz
     L.rle_tail_seg_workspace_bytes.argtypes = [u32, u64]
     L.rle_tail_batch_device_seg.restype = ctypes.c_int
@@ -656,6 +662,36 @@ def readn_reply_seg(d_streams, off, length, ulen, d_paths, path_off, path_len, d
                                             _ptr(path_off), _ptr(path_len), _ptr(d_out), cap, _ptr(place),
                                             _ptr(total), _ptr(status), form, n, tin, *_ws_ptr(ws),
                                             _stream_ptr(stream)), "rle_readn_reply_device_seg")
+
+
+def relocate_span_bytes(room: int) -> int:
+    """rle_relocate_span_bytes: the destination bytes one workgroup of relocate_batch's copy owns for
+    a room (dst_cap - dst_base) of this many bytes: a multiple of 16 KiB, about room / (8 * CUs).
+    Host only, 256 CUs without a device."""
+    return int(lib().rle_relocate_span_bytes(int(room)))
+
+
+def relocate_layout(length, want, sel, new_off, new_cap, total, dst_base=0, stream=None):
+    """rle_relocate_layout_device: new slots from sizes on the device, in one launch: a selected file
+    (sel None: all; else int32, non-zero) takes new_cap[i] = max(want[i], length[i]) rounded up to 16
+    (want None: 0), any other file 0; new_off[i] = dst_base + the caps before it and total[0] = the end
+    of the last slot (int64 device tensors)."""
+    _check(lib().rle_relocate_layout_device(_ptr(length), _ptr(want), _ptr(sel), int(dst_base), _ptr(new_off),
+                                            _ptr(new_cap), _ptr(total), length.numel(), _stream_ptr(stream)),
+           "rle_relocate_layout_device")
+
+
+def relocate_batch(d_src, off, length, d_dst, new_off, new_cap, total, want=None, sel=None, status=None, dst_base=0,
+                   dst_cap=None, stream=None):
+    """rle_relocate_batch_device: relocate_layout, then one copy of every selected stream
+    (d_src + off[i], length[i] bytes) to its new slot d_dst + new_off[i].  dst_cap (default: d_dst's
+    size) bounds the end of the last slot and, with dst_base, sizes the grid: pass the room this
+    relocation may take.  Slots that end past it leave d_dst untouched, every selected file
+    RLE_STATUS_NOFIT, and new_off / new_cap / total say what it takes."""
+    cap = d_dst.numel() if dst_cap is None else int(dst_cap)
+    _check(lib().rle_relocate_batch_device(_ptr(d_src), _ptr(off), _ptr(length), _ptr(want), _ptr(sel), _ptr(d_dst),
+                                           int(dst_base), cap, _ptr(new_off), _ptr(new_cap), _ptr(total), _ptr(status),
+                                           off.numel(), _stream_ptr(stream)), "rle_relocate_batch_device")
 
 
 def copy_device(dst, src, nbytes, stream=None):

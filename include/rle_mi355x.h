@@ -36,7 +36,10 @@
  * (tests/test_gpu_readn_pack_seg_replay.py; the same, with the segment length and table sizes frozen
  * from total_in_bytes), rle_readn_headers_device, rle_readn_reply_device, rle_readn_reply_device_seg
  * (tests/test_gpu_readn_reply_replay.py; n, form and out_cap are frozen, names and lengths are read
- * again) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
+ * again), rle_relocate_layout_device, rle_relocate_batch_device (tests/test_gpu_relocate_replay.py; n,
+ * dst_base, dst_cap and with them the span and the grid are frozen, lengths, wants, masks, offsets and
+ * data are read again and d_new_off, d_new_cap, d_total and the status words written again by each
+ * replay) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
  * (global) capture mode, and the graph replayed any number of times.  The host freezes at capture
  * what it decides itself: the kernel form (from n, the max_* hints and the cooperative mode), the
  * grid, the segment length and table sizes (from the total_* hint), every pointer including the
@@ -568,6 +571,91 @@ int rle_readn_reply_device_seg(const void* d_streams, const uint64_t* d_off, con
                                const uint64_t* d_path_len, void* d_out, uint64_t out_cap, uint64_t* d_place,
                                uint64_t* d_total, uint32_t* d_status, uint32_t form, uint32_t n,
                                uint64_t total_in_bytes, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- relocating stored streams: slots from sizes, one copy -------------------------
+ * The reference's write path ends by swapping in a freshly allocated block of exactly C' bytes and
+ * freeing the victims' (src/filesystemApi.c:811-814).  For streams kept in device arenas the same step
+ * is a move: after the size query, the files whose slots are too small go to slots of d_need bytes;
+ * after an eviction or a removeFile, the survivors are packed and the victims' slots given up.  These
+ * entries lay the new slots out from sizes that live on the device and move the streams there in one
+ * copy launch, with no copy of the sizes to the host and no synchronise.
+ *
+ * Selection and slot size, the same in both entries.  File i is selected when d_sel == NULL or
+ * d_sel[i] != 0; an unselected file is an evicted or removed one, or one that stays where it is.
+ * want_i = d_want ? d_want[i] : 0.  A selected file takes a slot of
+ *   cap_i = round_up_16(max(want_i, d_len[i]))
+ * bytes; an unselected file, and a selected one with max(want_i, d_len[i]) > RLE_MAX_BUFFER_BYTES, takes
+ * none (cap_i = 0).  The size query's d_need serves as d_want as it is: a file whose append was refused
+ * has d_need = 0 and keeps a slot for the stream it has, and A == 0 gives d_need = C.
+ *
+ * rle_relocate_layout_device: the slots, in 64 bits:
+ *   d_new_off[i] = dst_base + sum over k < i of cap_k      (non-decreasing)
+ *   d_new_cap[i] = cap_i                                   (0: file i has no new place)
+ *   *d_total     = dst_base + sum over all n of cap_k      (the end of the last slot)
+ * all three written for every file.  One launch of one workgroup, no workspace, no allocation and no
+ * host synchronisation.  Use it alone to ask how large the new arena must be before allocating it, or
+ * to pack the survivors of an eviction.  On the host: a NULL d_total, with n > 0 a NULL d_len,
+ * d_new_off or d_new_cap, dst_base not a multiple of 16, or n past the library's launch bound (2^30) is
+ * RLE_E_INVAL; n == 0 writes *d_total = dst_base and is RLE_OK.
+ *
+ * rle_relocate_batch_device: two launches, the layout and then one copy launch.  The copy reads
+ * *d_total: when *d_total > dst_cap every selected file gets RLE_STATUS_NOFIT and no byte of d_dst is
+ * written; d_new_off, d_new_cap and *d_total are written all the same (rle_readn_batch_device's rule).
+ * Otherwise, per file, in this order:
+ *   unselected                RLE_STATUS_OK, nothing written
+ *   RLE_STATUS_TOOLARGE       selected, d_len[i] or want_i past RLE_MAX_BUFFER_BYTES: no slot, nothing
+ *                             written
+ *   RLE_STATUS_MISALIGNED     d_src + d_off[i] is not 16-byte aligned: the slot stays reserved and
+ *                             untouched
+ *   RLE_STATUS_OK             the slot is d_dst + d_new_off[i]: [0, C) is the stream (C = d_len[i]),
+ *                             [C, round_up_16(C)) is zero, [round_up_16(C), cap_i) is untouched
+ * No other byte changes: no byte of d_dst below dst_base, at or past *d_total or in another file's
+ * slot, no byte of d_src; d_off, d_len and the caller's d_ulen and d_tail are not written.  The tail
+ * word's offset is relative to the stream and carries over as it is: the caller goes on with
+ * d_off <- d_new_off and d_cap <- d_new_cap.  The source is read up to round_up_16(C), which the
+ * store's slot rule makes readable.  d_want, d_sel and d_status may be NULL.
+ * The caller's duties: the destination range [dst_base, *d_total) of d_dst overlaps no selected source
+ * stream (two arenas, or one arena with dst_base past its used end; an in-place slide is not offered:
+ * it needs an order between workgroups), and d_new_off and d_new_cap do not alias d_off
+ * or d_len.
+ * On the host: n == 0 is RLE_OK and writes *d_total = dst_base when d_total is given; a NULL d_src,
+ * d_off, d_len, d_dst, d_new_off, d_new_cap or d_total, a d_dst that is not 16-byte aligned, dst_base
+ * not a multiple of 16, or dst_base > dst_cap is RLE_E_INVAL before any launch.
+ *
+ * The copy is balanced over destination bytes, not over files: with room = dst_cap - dst_base,
+ * workgroup w of ceil(room / span) owns the destination bytes [dst_base + w * span, + span) below
+ * *d_total, span = rle_relocate_span_bytes(room) = max(16 KiB, ceil(room / (8 * CUs))) rounded up to
+ * 16 KiB (256 CUs assumed when no device is usable), and returns at once when that range is empty.  It
+ * finds the file that owns its first byte by a 64-way search over d_new_off and walks forward from
+ * there; a slot across a span edge is written by both neighbours, each 16-byte chunk by exactly one.
+ * So dst_cap also sizes the grid: pass the room this relocation may take, not the size of the arena.
+ * Loads and stores are non-temporal from a room of 256 MiB (rle_copy_device's rule), decided on the
+ * host.
+ *
+ * rle_relocate_span_bytes (host only, launches nothing): that span for a room of room_bytes on the
+ * current device.  Tests use it to name the span edges.
+ *
+ * Measured on one MI355X (profiles/relocate.json and _run2.json, two fresh runs), with
+ * slots as tight as the streams and with worst-case append slots (2.5 times the stream: mostly gaps).
+ * Against rle_copy_device of the same number of copied bytes in one contiguous range, the ceiling: one
+ * stream of 4 KiB, 64 KiB or 1 MiB 12-20 us against 8-13 us, 4096 streams of 4 KiB 20-40 us against
+ * 9-17 us, 64 of 1 MiB 29-39 us against 25-29 us, 4096 of 64 KiB 109-139 us against 88-96 us: 1.16-1.44
+ * times the plain copy on the two largest shapes and 1.5-2.5 times on the small ones (the layout
+ * launch, the search, and at 4 KiB one load in flight per lane and slot); 0.48-0.61 of 8 TB/s on the
+ * two largest shapes, where the plain copy reaches 0.60-0.76.  Against what a caller had to do before
+ * (d_len and d_want copied to the host with a synchronise, the slots laid out there, the offsets
+ * uploaded, one hipMemcpyAsync device-to-device per file): one stream 12-20 us against 43-63 us, 64
+ * streams of 4 KiB or 64 KiB 13-25 us against 233-263 us, 64 of 1 MiB 29-39 us against 234-252 us, 4096
+ * streams 20-139 us against 12.4-16.1 ms.  The host route won on no shape measured. */
+uint64_t rle_relocate_span_bytes(uint64_t room_bytes);
+int rle_relocate_layout_device(const uint64_t* d_len, const uint64_t* d_want, const uint32_t* d_sel,
+                               uint64_t dst_base, uint64_t* d_new_off, uint64_t* d_new_cap,
+                               uint64_t* d_total, uint32_t n, void* stream);
+int rle_relocate_batch_device(const void* d_src, const uint64_t* d_off, const uint64_t* d_len,
+                              const uint64_t* d_want, const uint32_t* d_sel,
+                              void* d_dst, uint64_t dst_base, uint64_t dst_cap,
+                              uint64_t* d_new_off, uint64_t* d_new_cap, uint64_t* d_total,
+                              uint32_t* d_status, uint32_t n, void* stream);
 
 /* Diagnostic builds only (RLE_STAMPS=1, never the product library): per-segment decode cycle sums
  * over all waves: [tile wait, scan, scatter, flush reads, flush fill, flush store, flush re-zero,
