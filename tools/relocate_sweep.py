@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Relocating stored streams: rle_relocate_batch_device against the streaming copy of the same bytes
-and against what a caller had to do before, timed in one process on the same arenas (not bench.py;
-DESIGN.md §4d quotes the table).
+and against what a caller had to do before (DESIGN.md §4d quotes the table; the method is
+tools/sweeplib.py's).
 
   r  relocation      rle_relocate_batch_device: the layout launch and the copy launch that follows the
                      per-file map on the device; sizes never leave the device
@@ -15,38 +15,33 @@ DESIGN.md §4d quotes the table).
 Per shape (n streams of C bytes each, random bytes: a copy does not care): the streams packed in the
 source arena; twice, with want = C (slots as tight as the streams) and with want = the worst-case slot
 of an append of as many bytes again (rle_append_slot_bytes(C, C): gaps larger than the streams).
-dst_cap is the layout's total: the room this relocation takes.  `reps` replicas of the source and of
-every destination arena, device events around `reps` back-to-back calls (one per replica; h's copy to
-the host makes each of its calls wait for the one before), a warm-up round, the forms alternating over
-`rounds` rounds, median / min / max in us per call.  Before any timing the outputs are compared: r's
-destination with h's, byte for byte over the poison, and r's with m's where the slots are tight.  A
-form counts as faster or slower than another only when the medians differ by more than the two forms'
-min-max spreads together.
+dst_cap is the layout's total: the room this relocation takes.  Replicas of the source and of every
+destination arena; h's copy to the host makes each of its calls wait for the one before.  Before any
+timing the outputs are compared: r's destination with h's, byte for byte over the poison, and r's
+with m's where the slots are tight.
 
-usage: python tools/relocate_sweep.py [--rounds 7] [--sizes 4096,65536] [--out profiles/relocate.json]"""
-import argparse
+usage: python tools/relocate_sweep.py [--rounds 7] [--sizes 4096,65536] [--shapes 0,3] [--out profiles/relocate.json]"""
 import ctypes
-import json
-import os
-import sys
+import functools
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(REPO, "c-filestorage-server-and-client_amd")]
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import rle_mi355x as R  # noqa: E402
+import numpy as np
+import sweeplib as S
+import torch
+from sweeplib import R
 
 SHAPES = ((1, 4096, 8), (64, 4096, 8), (4096, 4096, 8), (1, 65536, 8), (64, 65536, 8), (4096, 65536, 3),
           (1, 1 << 20, 8), (64, 1 << 20, 4))   # (n, C, reps)
 POISON = 0xA5
 D2D = 3   # hipMemcpyDeviceToDevice
+FORMS = {"r": "rle_relocate_batch_device (layout launch + one copy launch)",
+         "m": "rle_copy_device of the same number of copied bytes, one contiguous range (the ceiling)",
+         "h": "d_len and d_want copied to the host with a synchronise, the slots laid out there, the "
+              "offsets and capacities uploaded, one hipMemcpyAsync device-to-device per file"}
+SLOTS = {"tight": "want = C", "worst-case": "want = rle_append_slot_bytes(C, C)"}
+TIMING = S.timing_text("call", "the arenas", "streams")
 
 
-def r16(x):
-    return (x + 15) & ~15
-
-
+@functools.lru_cache(None)
 def hip_runtime():
     """The HIP runtime this process already uses (torch's), for the host route's hipMemcpyAsync."""
     with open("/proc/self/maps") as f:
@@ -58,11 +53,12 @@ def hip_runtime():
     return hip
 
 
-def shape(n, C, slots, reps, rounds, dev, hip):
+def shape(a, s, slots, dev):
+    (n, C, reps), rounds, hip = s, a.rounds, hip_runtime()
     i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)   # noqa: E731
     assert C % 16 == 0
     want_h = [C if slots == "tight" else R.append_slot_bytes(C, C)] * n
-    cap = r16(max(want_h[0], C))
+    cap = S.r16(max(want_h[0], C))
     total = n * cap
     src = torch.randint(0, 256, (reps, n * C), dtype=torch.uint8, device=dev)
     soff_h = [i * C for i in range(n)]
@@ -73,8 +69,7 @@ def shape(n, C, slots, reps, rounds, dev, hip):
     new_cap = {k: torch.zeros(n, dtype=torch.int64, device=dev) for k in "rh"}
     d_total = torch.zeros(1, dtype=torch.int64, device=dev)
     status = torch.zeros(n, dtype=torch.int32, device=dev)
-    s = torch.cuda.current_stream()
-    sp = ctypes.c_void_p(s.cuda_stream)
+    sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def form_r(k):
         R.relocate_batch(src[k], off, length, dst["r"][k], new_off["r"], new_cap["r"], d_total, want=want,
@@ -106,84 +101,28 @@ def shape(n, C, slots, reps, rounds, dev, hip):
     assert bool((dst["r"][0].view(n, cap)[:, C:] == POISON).all()), "r wrote into a gap"
     assert torch.equal(dst["m"][0], src[0])
 
-    forms = (("r", form_r), ("m", form_m), ("h", form_h))
-    times = {name: [] for name, _ in forms}
-    for rnd in range(rounds + 1):   # round 0 warms every form at this shape
-        for name, fn in forms:
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            for k in range(reps):
-                fn(k)
-            e1.record(s)
-            torch.cuda.synchronize()
-            if rnd:
-                times[name].append(e0.elapsed_time(e1) / reps * 1e3)
-    room = total
-    row = {"n": n, "C": C, "slots": slots, "want": want_h[0], "copied_bytes": n * C, "room_bytes": room,
-           "span_bytes": R.relocate_span_bytes(room), "reps": reps, "rounds": rounds, "outputs_equal": True}
-    for name in times:
-        v = sorted(times[name])
-        row[name] = {"median_us": round(v[len(v) // 2], 2), "min_us": round(v[0], 2), "max_us": round(v[-1], 2)}
+    times = S.time_forms((("r", form_r), ("m", form_m), ("h", form_h)), reps, rounds)
+    row = {"n": n, "C": C, "slots": slots, "want": want_h[0], "copied_bytes": n * C, "room_bytes": total,
+           "span_bytes": R.relocate_span_bytes(total), "reps": reps, "rounds": rounds, "outputs_equal": True}
+    row.update((name, S.stats(v)) for name, v in times.items())
     row["r_copy_GBps"] = round(2 * n * C / row["r"]["median_us"] / 1e3, 1)   # bytes read + bytes written
-    spread = lambda f: row[f]["max_us"] - row[f]["min_us"]   # noqa: E731
     for other in "mh":
-        d = row["r"]["median_us"] - row[other]["median_us"]
-        sp_ = spread("r") + spread(other)
-        row["r_over_" + other] = round(row["r"]["median_us"] / row[other]["median_us"], 3)
-        row["r_minus_" + other + "_us"] = round(d, 2)
-        row["r_spread_with_" + other + "_us"] = round(sp_, 2)
-        row["r_vs_" + other] = "slower" if d > sp_ else ("faster" if -d > sp_ else "within the spread")
+        S.verdict(row, "r", other)
     return row
 
 
-def size_name(c):
-    return f"{c >> 20} MiB" if c >= 1 << 20 else f"{c >> 10} KiB"
-
-
 def table(rows):
-    out = ["| streams x C | slots | r | m | h | r / m | r / h |", "|---|---|---|---|---|---|---|"]
-    cell = lambda r, k: f"{r[k]['median_us']:.1f} ({r[k]['min_us']:.1f}-{r[k]['max_us']:.1f})"   # noqa: E731
-    for r in rows:
-        out.append(f"| {r['n']} x {size_name(r['C'])} | {r['slots']} | {cell(r, 'r')} | {cell(r, 'm')} | {cell(r, 'h')} | "
-                   f"{r['r_over_m']:.2f} {r['r_vs_m']} | {r['r_over_h']:.2f} {r['r_vs_h']} |")
-    return "\n".join(out)
+    return S.table(["streams x C", "slots", "r", "m", "h", "r / m", "r / h"], rows,
+                   lambda r: [f"{r['n']} x {S.size_name(r['C'])}", r["slots"], *(S.cell(r, k) for k in "rmh"),
+                              S.ratio_cell(r, "r", "m"), S.ratio_cell(r, "r", "h")])
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--sizes", default="", help="comma-separated stream sizes C to run (default: all)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "relocate.json"))
-    a = ap.parse_args()
-    assert torch.cuda.is_available(), "relocate_sweep.py measures on an MI355X"
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(0)
-    hip = hip_runtime()
-    rows = []
+def keep(a, s):
     sizes = {int(c) for c in a.sizes.split(",") if c}
-    for n, C, reps in SHAPES:
-        if sizes and C not in sizes:
-            continue
-        for slots in ("tight", "worst-case"):
-            rows.append(shape(n, C, slots, reps, a.rounds, dev, hip))
-            print(json.dumps(rows[-1]), flush=True)
-            torch.cuda.empty_cache()
-    res = {"tool": "tools/relocate_sweep.py", "device": torch.cuda.get_device_name(0), "library": R.version(),
-           "forms": {"r": "rle_relocate_batch_device (layout launch + one copy launch)",
-                     "m": "rle_copy_device of the same number of copied bytes, one contiguous range (the ceiling)",
-                     "h": "d_len and d_want copied to the host with a synchronise, the slots laid out there, the "
-                          "offsets and capacities uploaded, one hipMemcpyAsync device-to-device per file"},
-           "slots": {"tight": "want = C", "worst-case": "want = rle_append_slot_bytes(C, C)"},
-           "timing": "device events around `reps` back-to-back calls (one per replica of the arenas), forms "
-                     "alternating over `rounds` rounds after a warm-up round; us per call of n streams; median (min-max)",
-           "rows": rows, "table": table(rows).split("\n")}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(table(rows))
+    return not sizes or s[1] in sizes
 
 
 if __name__ == "__main__":
-    main()
+    S.main(__file__, shape, SHAPES, {"forms": FORMS, "slots": SLOTS, "timing": TIMING}, "relocate.json", kinds=False,
+           variants=tuple(SLOTS), keep=keep, table=table,
+           options=[("--sizes", dict(default="", help="comma-separated stream sizes C to run (default: all)"))])
