@@ -1390,3 +1390,6 @@ extern "C" const char* rle_mi355x_version(void) { return "rle_mi355x 0.3 (gfx950
 
 // ================================================================ relocating stored streams
 #include "rle_relocate.h"
+
+// ================================================================ choosing eviction victims
+#include "rle_evict.h"

@@ -35,6 +35,10 @@ RLE_LAUNCH_STATUS_FLAG = 2
 RLE_REPLY_READN = 0
 RLE_REPLY_READ = 1
 RLE_REPLY_END = 0x100
+RLE_EVICT_SLOTS = 1
+RLE_EVICT_SUMMARY_WORDS = 6
+RLE_EVICT_ORDER_EVICTION = 0
+RLE_EVICT_ORDER_REPLY = 1
 
 _u64p = ctypes.c_void_p
 _lib = None
@@ -154,6 +158,10 @@ def lib():
     L.rle_relocate_layout_device.argtypes = [vp, vp, vp, u64, vp, vp, vp, u32, vp]
     L.rle_relocate_batch_device.restype = ctypes.c_int
     L.rle_relocate_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, vp, vp, vp, vp, u32, vp]
+    L.rle_evict_select_device.restype = ctypes.c_int
+    L.rle_evict_select_device.argtypes = [vp, vp, vp, vp, vp, u64, u32, u32, vp, vp, vp, u32, vp]
+    L.rle_evict_gather_device.restype = ctypes.c_int
+    L.rle_evict_gather_device.argtypes = [vp, vp, u32, vp, vp, u32, u32, vp]
     L.rle_tail_seg_workspace_bytes.restype = sz
     L.rle_tail_seg_workspace_bytes.argtypes = [u32, u64]
     L.rle_tail_batch_device_seg.restype = ctypes.c_int
@@ -692,6 +700,35 @@ def relocate_batch(d_src, off, length, d_dst, new_off, new_cap, total, want=None
     _check(lib().rle_relocate_batch_device(_ptr(d_src), _ptr(off), _ptr(length), _ptr(want), _ptr(sel), _ptr(d_dst),
                                            int(dst_base), cap, _ptr(new_off), _ptr(new_cap), _ptr(total), _ptr(status),
                                            off.numel(), _stream_ptr(stream)), "rle_relocate_batch_device")
+
+
+def evict_select(key, length, keep, victims, summary, want=None, live=None, spare=None, max_bytes=(1 << 64) - 1,
+                 max_files=0, flags=0, stream=None):
+    """rle_evict_select_device: the eviction victims from keys and sizes on the device, in one launch:
+    the eligible files (live None: all, else int32 non-zero; spare None: none spared) in ascending
+    (key[i], i) order, unsigned, until the live files' sizes (max(want[i], length[i]), want None: 0;
+    rounded up to 16 under RLE_EVICT_SLOTS) sum to max_bytes at most and, with max_files != 0, the live
+    files are max_files at most.  keep[i] (int32) = 1 for a live file that stays, victims[0:m] (int32)
+    the victims in eviction order, summary (int64, RLE_EVICT_SUMMARY_WORDS) = status, m, bytes before
+    and after, live files before and after.  key, length, want: int64 device tensors, read as unsigned."""
+    _check(lib().rle_evict_select_device(_ptr(key), _ptr(length), _ptr(want), _ptr(live), _ptr(spare), int(max_bytes),
+                                         int(max_files), int(flags), _ptr(keep), _ptr(victims), _ptr(summary),
+                                         length.numel(), _stream_ptr(stream)), "rle_evict_select_device")
+
+
+def evict_gather(victims, summary, tables_in, tables_out, order=RLE_EVICT_ORDER_EVICTION, cap=None, stream=None):
+    """rle_evict_gather_device: row j of every tables_out[k] from row victims[j] (or, in
+    RLE_EVICT_ORDER_REPLY, victims[m - 1 - j]) of tables_in[k], for j < min(m, cap) with m = summary[1]
+    read on the device; 1 to 8 int64 tables; cap (default: the first output table's size) bounds the
+    rows written."""
+    k = len(tables_in)
+    if len(tables_out) != k:
+        raise RLEError("rle_evict_gather_device: as many output tables as input tables")
+    cap = (tables_out[0].numel() if k else 0) if cap is None else int(cap)
+    tin = (ctypes.c_void_p * max(k, 1))(*[t.data_ptr() for t in tables_in])
+    tout = (ctypes.c_void_p * max(k, 1))(*[t.data_ptr() for t in tables_out])
+    _check(lib().rle_evict_gather_device(_ptr(victims), _ptr(summary), int(order), tin, tout, k, cap,
+                                         _stream_ptr(stream)), "rle_evict_gather_device")
 
 
 def copy_device(dst, src, nbytes, stream=None):

@@ -39,6 +39,9 @@
  * again), rle_relocate_layout_device, rle_relocate_batch_device (tests/test_gpu_relocate_replay.py; n,
  * dst_base, dst_cap and with them the span and the grid are frozen, lengths, wants, masks, offsets and
  * data are read again and d_new_off, d_new_cap, d_total and the status words written again by each
+ * replay), rle_evict_select_device, rle_evict_gather_device (tests/test_gpu_evict_replay.py; n, the
+ * limits, flags, order, cap, ntables and the table pointers are frozen, keys, sizes, masks and the
+ * summary are read again and d_keep, d_victims, d_summary and the gathered rows written again by each
  * replay) and rle_append_prepare_device -- may be called on a stream that is being captured, in the default
  * (global) capture mode, and the graph replayed any number of times.  The host freezes at capture
  * what it decides itself: the kernel form (from n, the max_* hints and the cooperative mode), the
@@ -656,6 +659,107 @@ int rle_relocate_batch_device(const void* d_src, const uint64_t* d_off, const ui
                               void* d_dst, uint64_t dst_base, uint64_t dst_cap,
                               uint64_t* d_new_off, uint64_t* d_new_cap, uint64_t* d_total,
                               uint32_t* d_status, uint32_t n, void* stream);
+
+/* ---- choosing eviction victims: in policy order until it fits -----------------------
+ * The reference decides evictions between the size and the swap of a write, in writeToFileHandler:
+ *   while (currStorageSize - contentSize + newCompressedSize > maxStorageSize) victim = getVictim(store, fptr)
+ * (src/filesystemApi.c:784-798), and in openFileHandler when the file count is at its limit (:477-480).
+ * getVictim (:41-64, comparators in src/cacheFns.c:9-21) picks the file with the smallest policy key --
+ * the insertion time for FIFO, lastRef for LRU, refCount for LFU -- the earliest in list order among
+ * equals, and never the file being written.  The sizes that decide it (d_len, and the d_need of the
+ * pending appends) live on the device; these entries take the decision there, so that the write path's
+ * "size -> refuse / evict / relocate -> fit" runs without copying a size to the host.
+ *
+ * rle_evict_select_device.  Definitions:
+ *   live      d_live == NULL or d_live[i] != 0
+ *   spared    d_spare != NULL and d_spare[i] != 0: the files this batch writes to (getVictim's `spare`)
+ *   eligible  live and not spared
+ *   size_i    max(d_want ? d_want[i] : 0, d_len[i]); under RLE_EVICT_SLOTS rounded up to 16.  This is the
+ *             rule of rle_relocate_layout_device, so the size query's d_need serves as d_want as it is.
+ *             A file that is not live counts nothing.
+ *   order     the eligible files ascending by (d_key[i], i).  Keys compare as plain unsigned 64-bit
+ *             integers (the reference's comparators return a time_t or size_t difference as int; that
+ *             truncation is not reproduced).  The index stands for the reference's list order: with all
+ *             keys equal the order is FIFO over the list.
+ * The victims are the shortest prefix of that order after whose removal both hold:
+ *   bytes = the sum of size_i over the live files <= max_bytes, and
+ *   max_files == 0, or the number of live files <= max_files.
+ * This is the reference's while (... > maxStorageSize): a store that fits exactly evicts nothing.
+ * openFileHandler's single victim is max_files = maxFileNum - 1 with max_bytes = UINT64_MAX.
+ * Outputs, all written by every call:
+ *   d_keep[i]         1 for a live file that stays, 0 for a victim or a file that is not live: usable as
+ *                     d_sel of rle_relocate_batch_device as it is
+ *   d_victims[0, m)   the victims' indices in eviction order; entries at and past m are not written
+ *   d_summary[0..5]   status, m, bytes before, bytes after, live files before, live files after
+ * Refusals: the status goes to d_summary[0], m = 0, d_keep[i] = live_i, after = before, and d_victims is
+ * left untouched:
+ *   RLE_STATUS_TOOLARGE  some live file has max(want, len) > RLE_MAX_BUFFER_BYTES.  (Without one every
+ *                        sum stays below 2^62; with one the byte sums are taken modulo 2^64.)
+ *   RLE_STATUS_NOFIT     removing every eligible file still leaves the store over a limit: the
+ *                        reference's E2BIG, and the case in which its assert(victim) would fire
+ * On the host, before any launch: n == 0 is RLE_OK and writes the summary (all zero), so d_summary is
+ * required even then; a NULL d_summary, with n > 0 a NULL d_key, d_len, d_keep or d_victims, a flag bit
+ * other than RLE_EVICT_SLOTS, or n past the library's launch bound (2^30) is RLE_E_INVAL.  d_want, d_live
+ * and d_spare may be NULL.  d_keep must not alias d_live or d_spare.
+ * The caller keeps: the keys (when they are updated), LFU's reset of every refCount after an eviction
+ * (:800-805), and everything the host does with the victims' names.
+ *
+ * One launch of one workgroup of 1024 threads, no workspace, no allocation, no host synchronisation; no
+ * workgroup waits for anything and every loop is bounded by n.  One pass over the files sums bytes and
+ * counts over the live and the eligible files; a store that fits, and a refusal, end there.  Else the
+ * threshold key is found by a weighted radix select over the bytes of the key from the first byte the
+ * eligible keys do not share (a 256-bin LDS histogram of byte sums and counts per pass, both remaining
+ * needs reduced by the bins below the chosen one), an index-order scan over the files with that key
+ * finds the last one taken, the victims are compacted in index order and then sorted by (key, index)
+ * with a bitonic network: in LDS for m <= 4096, over d_victims in global memory beyond (slow, correct).
+ *
+ * rle_evict_gather_device: the victims' rows of up to 8 tables of 64-bit words, in one launch with a
+ * grid over cap.  tables_in and tables_out are host arrays of ntables (1..8) device pointers, passed to
+ * the kernel by value.  With m = d_summary[1] read on the device, for j < min(m, cap) and every table k:
+ *   tables_out[k][j] = tables_in[k][v],  v = d_victims[j]          (RLE_EVICT_ORDER_EVICTION)
+ *                                        v = d_victims[m - 1 - j]  (RLE_EVICT_ORDER_REPLY)
+ * Entries at and past m are not written.  The reply order is the reversed one: the reference builds
+ * evictedList by push-front (:792-793) and sends it from its head (src/server.c:314-323), last evicted
+ * first.  With d_off, d_len, d_ulen, d_path_off and d_path_len as the tables, the outputs are the
+ * arguments of rle_readn_reply_device(..., RLE_REPLY_READN | RLE_REPLY_END, n = m, ...): the reference's
+ * eviction reply.  The host must read m and the victim list before it can call the reply with n = m: one
+ * small device-to-host copy of d_summary and d_victims.  The host needs the list anyway, to drop the
+ * victims' names, log EVICTED and notify waiting clients; the sizes, the keys and the tables never
+ * leave the device.  After the eviction a victim's row of the caller's tables is dead: the relocation
+ * gives it no slot (d_new_cap[i] = 0), and what a later append reports for it says nothing.
+ * On the host, checked in this order: a NULL d_victims, d_summary, tables_in or
+ * tables_out, ntables of 0 or above 8, an unknown order, or a NULL table pointer is RLE_E_INVAL; then
+ * cap == 0 is RLE_OK and launches nothing.
+ *
+ * Graph capture (tests/test_gpu_evict_replay.py): n, max_bytes, max_files, flags, order, cap, ntables
+ * and every pointer (the table pointers among them) are frozen at capture; keys, sizes, masks and the
+ * summary are read again, and every output written again, by each replay.
+ *
+ * Measured on one MI355X (profiles/evict.json and _run2.json, two fresh runs), against
+ * what a caller had to do before (keys, sizes and masks copied to the host with a synchronise, a numpy
+ * lexsort and cumsum there, the keep mask and five gathered tables uploaded).  The selection alone: a
+ * store that fits 17-26 us at 64 files, 16-36 us at 4096, 107-158 us at 65536, against 107-143 us,
+ * 149-244 us and 3.1-6.8 ms; 1 % or 10 % evicted 20-47 us, 39-58 us and 316-620 us against 126-395 us,
+ * 181-331 us and 3.2-4.3 ms; every eligible file evicted 24-40 us at 64 files and 112-125 us at 4096
+ * (3712 victims, the LDS sort) against 127-300 us and 206-689 us.  With the gather 5-14 us more where
+ * the selection is short.  The host route won on one shape: all 59392 eligible of 65536 files evicted
+ * at once, the sort in global memory, 4.05-4.07 ms against 3.5-8.3 ms (3.59 ms in the quiet run).  A
+ * caller that expects to evict tens of thousands of files in one step should take the host route
+ * there; below a few thousand victims the device route was faster at every n measured. */
+#define RLE_EVICT_SLOTS 1u        /* count round_up_16(size): what rle_relocate_layout_device lays out.
+                                     Without it: exact bytes, the reference's currStorageSize */
+#define RLE_EVICT_SUMMARY_WORDS 6
+#define RLE_EVICT_ORDER_EVICTION 0u
+#define RLE_EVICT_ORDER_REPLY    1u   /* reversed: evictedList is built by push-front (:792-793) and sent from
+                                         its head (src/server.c:314-323), last evicted first */
+int rle_evict_select_device(const uint64_t* d_key, const uint64_t* d_len, const uint64_t* d_want,
+                            const uint32_t* d_live, const uint32_t* d_spare,
+                            uint64_t max_bytes, uint32_t max_files, uint32_t flags,
+                            uint32_t* d_keep, uint32_t* d_victims, uint64_t* d_summary,
+                            uint32_t n, void* stream);
+int rle_evict_gather_device(const uint32_t* d_victims, const uint64_t* d_summary, uint32_t order,
+                            const uint64_t* const* tables_in, uint64_t* const* tables_out,
+                            uint32_t ntables, uint32_t cap, void* stream);
 
 /* Diagnostic builds only (RLE_STAMPS=1, never the product library): per-segment decode cycle sums
  * over all waves: [tile wait, scan, scatter, flush reads, flush fill, flush store, flush re-zero,

@@ -1,7 +1,7 @@
 """What the same-process sweep tools share: the setup of stored files on the device, the timing
 loop, the statistics, the verdict rule, the table writer and the main.  (append_sweep,
 append_seg_sweep, append_fit_sweep, tail_seg_sweep, readn_pack_sweep, readn_pack_seg_sweep,
-readn_reply_sweep and relocate_sweep import it; not bench.py, and no tool of its own.)
+readn_reply_sweep, relocate_sweep and evict_sweep import it; not bench.py, and no tool of its own.)
 
 The method, once for all of them.  A tool times a few forms of the same work in one process on the
 same files.  Per shape it makes `reps` replicas of every arena a call reads or writes, so that
