@@ -150,10 +150,22 @@ __device__ __forceinline__ u32 lds_addr(const void* p) {
 // VGPR is in flight that the compiler could copy or reuse before the data lands.  (The non-
 // temporal hint on the tile loads and on the large launches' stores measured slower everywhere,
 // r3n: DESIGN.md §4.)
-template <bool kStream = false>
+// kFreeM0 (the small-batch kernels, kLean below): M0 is set and left.  The compiler reserves M0 and
+// keeps nothing in it across a statement, and those kernels' listings hold no other use of it, so the
+// save and the restore around every tile load are two scalar instructions for nothing.
+template <bool kStream = false, bool kFreeM0 = false>
 __device__ __forceinline__ void dma_tile(u32x4 rs, u32 voff, u32 lds) {
     u32 keep;
-    if (kStream)
+    if (kFreeM0)
+        asm volatile(
+            "s_mov_b32 m0, %1\n\t"
+            "s_waitcnt lgkmcnt(0)\n\t"   // earlier ds_reads of this slot have completed
+            "s_nop 0\n\t"
+            "buffer_load_dwordx4 %0, %2, 0 offen lds"
+            :
+            : "v"(voff), "s"(lds), "s"(rs)
+            : "memory");
+    else if (kStream)
         asm volatile(
             "s_mov_b32 %0, m0\n\t"
             "s_mov_b32 m0, %2\n\t"
@@ -213,6 +225,32 @@ __device__ __forceinline__ void vm_wait(u32 n) {
     }
 }
 #undef RLE_VMW
+// vm_wait for a walk whose count is nearly always 3 or 2 (the small-batch decode's literal path).
+// hipcc lowers the switch above to a tree of four compares with their branches and mask moves, 19
+// scalar instructions on the way to vmcnt(3) on every step.  Here the counts up to 3 are a cascade inside one statement
+// (waiting for 3, then 2, ... is waiting for the smallest): 5 scalar instructions for 3, 8 for 2;
+// a larger count skips the cascade and takes the switch.  The wait is the same count either way.
+__device__ __forceinline__ void vm_wait_low(u32 n) {
+    n = uniform(n);
+    asm volatile(
+        "s_cmp_gt_u32 %0, 3\n\t"
+        "s_cbranch_scc1 .Lvmw_%=\n\t"
+        "s_waitcnt vmcnt(3)\n\t"
+        "s_cmp_gt_u32 %0, 2\n\t"
+        "s_cbranch_scc1 .Lvmw_%=\n\t"
+        "s_waitcnt vmcnt(2)\n\t"
+        "s_cmp_gt_u32 %0, 1\n\t"
+        "s_cbranch_scc1 .Lvmw_%=\n\t"
+        "s_waitcnt vmcnt(1)\n\t"
+        "s_cmp_gt_u32 %0, 0\n\t"
+        "s_cbranch_scc1 .Lvmw_%=\n\t"
+        "s_waitcnt vmcnt(0)\n"
+        ".Lvmw_%=:"
+        :
+        : "s"(n)
+        : "memory", "scc");
+    if (n > 3u) vm_wait(n);
+}
 // the same for the walks whose counts reach past 15 (enc_stream_body)
 #define RLE_VMW2(N)                                           \
     case N:                                                   \
@@ -273,28 +311,49 @@ struct Refill {
     u32 lds;     // slot LDS address
     bool on;     // tile t+2 exists (wave-uniform)
     bool look;   // kLook walks: lane 0 also loads the 16 bytes after the tile into the slot's tail
+    bool free_m0 = false;   // kLeanM0 walks: M0 is not preserved (dma_tile)
     __device__ __forceinline__ void operator()() const {
         if (on) {
-            dma_tile<true>(rs, voff, lds);
-            if (look) dma_tile<true>(rs, voff + kEncStep, lds + kSlot);
+            if (free_m0) {
+                dma_tile<true, true>(rs, voff, lds);
+                if (look) dma_tile<true, true>(rs, voff + kEncStep, lds + kSlot);
+            } else {
+                dma_tile<true>(rs, voff, lds);
+                if (look) dma_tile<true>(rs, voff + kEncStep, lds + kSlot);
+            }
         }
     }
 };
+// kLean: the shorter scalar stream of the small-batch instantiations (encode_kernel<2, 1>,
+// decode_kernel<192, 0, 1>; DESIGN.md §4, "per-wave instruction stream").  Every other kernel walks
+// with kLean = 0 and keeps its instruction stream.
+constexpr u32 kLeanM0 = 1u;     // tile loads leave M0 set (dma_tile<., true>)
+constexpr u32 kLeanWait = 2u;   // the literal path's wait counts without the switch (vm_wait_low)
+constexpr u32 kLeanTable = 4u;  // decode: the shared tables' loads ahead of wave 0's tiles (dec_prologue; not taken)
+// The items taken, per kernel (profiles/istream_ab.md): encode both; decode the waits only (the M0
+// item alone cost its decode 1-2 %, the table item 1-2.6 % on zero-filled and lone-wave batches).
+// A/B builds (make variant DEFS=-DRLE_ISTREAM=<bits>) set both kernels' items; 0 is the stream as it was.
+#ifdef RLE_ISTREAM
+constexpr u32 kLeanEnc = RLE_ISTREAM, kLeanDec = RLE_ISTREAM;
+#else
+constexpr u32 kLeanEnc = kLeanM0 | kLeanWait, kLeanDec = kLeanWait;
+#endif
 // Tiles start at `start` (bytes from the buffer descriptor's base): tile t is [start + 1008 t, ...).
 // The first two tiles' loads; walk_tiles issues them itself unless the caller did (primed), e.g. to
 // overlap their latency with its own setup.
 // kStep: tile stride; kLook: encode tiles (kEncStep, slots of kEncSlot with the lookahead load).
-template <u32 kStep = kTileStep, bool kLook = false>
+template <u32 kStep = kTileStep, bool kLook = false, u32 kLean = 0u>
 __device__ __forceinline__ void walk_prime(u32x4 rs, u32 start, u32 ntiles, u32 lane, const uint8_t* slots) {
+    constexpr bool kM0 = (kLean & kLeanM0) != 0u;
     constexpr u32 kStride = kLook ? kEncSlot : kSlot;
     const u32 lo = start + 16u * lane;
     const u32 l0 = uniform(lds_addr(slots)), l1 = l0 + kStride;
     asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh
-    if (ntiles) Refill{rs, lo, l0, true, kLook && lane == 0u}();
-    if (ntiles > 1u) Refill{rs, kStep + lo, l1, true, kLook && lane == 0u}();
+    if (ntiles) Refill{rs, lo, l0, true, kLook && lane == 0u, kM0}();
+    if (ntiles > 1u) Refill{rs, kStep + lo, l1, true, kLook && lane == 0u, kM0}();
 }
 // Returns whether a step stopped the walk (~0u).
-template <u32 kStep = kTileStep, bool kLook = false, class Step>
+template <u32 kStep = kTileStep, bool kLook = false, u32 kLean = 0u, class Step>
 __device__ __forceinline__ bool walk_tiles(u32x4 rs, u32 start, u32 ntiles, u32 lane, const uint8_t* slots,
                                            Step step, bool primed = false) {
     constexpr u32 kStride = kLook ? kEncSlot : kSlot;
@@ -302,24 +361,30 @@ __device__ __forceinline__ bool walk_tiles(u32x4 rs, u32 start, u32 ntiles, u32 
     const u32 lo = start + 16u * lane;
     const u32 l0 = uniform(lds_addr(slots)), l1 = l0 + kStride;
     const bool look = kLook && lane == 0u;
+    constexpr bool kM0 = (kLean & kLeanM0) != 0u;
+    // a literal step is one store: with the next tile's load between two of them 3, without it 2
+    auto wait = [](u32 n) {
+        if (kLean & kLeanWait) vm_wait_low(n);
+        else vm_wait(n);
+    };
     // Only tiles that exist are loaded, so before step t the ops issued after tile t's load are
     // step t-2's stores, tile t+1's load (if t+1 < ntiles) and step t-1's stores.  Stores are never
     // waited for: nothing in the wave reads them back, and a wave may end with stores in flight.
     // Loads are all consumed by the last step, so only a walk that stops early (~0u) drains.
-    if (!primed) walk_prime<kStep, kLook>(rs, start, ntiles, lane, slots);
+    if (!primed) walk_prime<kStep, kLook, kLean>(rs, start, ntiles, lane, slots);
     u32 p1 = 0, p2 = 0;   // stores of the last step and of the one before
     for (u32 t = 0; t < ntiles; t += 2) {
-        vm_wait(p2 + (t + 1u < ntiles ? kLoads : 0u) + p1);
+        wait(p2 + (t + 1u < ntiles ? kLoads : 0u) + p1);
         p2 = p1;
-        p1 = step(t, slots, Refill{rs, (t + 2u) * kStep + lo, l0, t + 2u < ntiles, look});
+        p1 = step(t, slots, Refill{rs, (t + 2u) * kStep + lo, l0, t + 2u < ntiles, look, kM0});
         if (p1 == ~0u) {
             vm_drain();
             return true;
         }
         if (t + 1u >= ntiles) break;
-        vm_wait(p2 + (t + 2u < ntiles ? kLoads : 0u) + p1);
+        wait(p2 + (t + 2u < ntiles ? kLoads : 0u) + p1);
         p2 = p1;
-        p1 = step(t + 1u, slots + kStride, Refill{rs, (t + 3u) * kStep + lo, l1, t + 3u < ntiles, look});
+        p1 = step(t + 1u, slots + kStride, Refill{rs, (t + 3u) * kStep + lo, l1, t + 3u < ntiles, look, kM0});
         if (p1 == ~0u) {
             vm_drain();
             return true;
@@ -1217,27 +1282,33 @@ __device__ __forceinline__ u32 enc_pair(const uint8_t* slotA, const uint8_t* slo
 // A walk two tiles per step (slots A, B; the last tile of an odd count alone, in slot A).  As
 // walk_tiles: the wait before a step leaves only the previous step's stores in flight; a step
 // returning ~0u stops the walk (drained; returns true).
-template <u32 kStep = kTileStep, bool kLook = false, class Pair, class Single>
+template <u32 kStep = kTileStep, bool kLook = false, u32 kLean = 0u, class Pair, class Single>
 __device__ __forceinline__ bool walk_pairs(u32x4 rs, u32 start, u32 ntiles, u32 lane, const uint8_t* slots, Pair pair,
                                            Single single, bool primed = false) {
     constexpr u32 kStride = kLook ? kEncSlot : kSlot;
     const u32 lo = start + 16u * lane;
     const u32 l0 = uniform(lds_addr(slots)), l1 = l0 + kStride;
     const bool look = kLook && lane == 0u;
-    if (!primed) walk_prime<kStep, kLook>(rs, start, ntiles, lane, slots);
+    constexpr bool kM0 = (kLean & kLeanM0) != 0u;
+    // (before the first step nothing is stored yet: the count is 0 without the switch)
+    auto wait = [](u32 n) {
+        if ((kLean & kLeanWait) && n == 0u) vm_drain();
+        else vm_wait(n);
+    };
+    if (!primed) walk_prime<kStep, kLook, kLean>(rs, start, ntiles, lane, slots);
     u32 p1 = 0, t = 0;
     for (; t + 1u < ntiles; t += 2u) {
-        vm_wait(p1);
-        p1 = pair(t, slots, slots + kStride, Refill{rs, (t + 2u) * kStep + lo, l0, t + 2u < ntiles, look},
-                  Refill{rs, (t + 3u) * kStep + lo, l1, t + 3u < ntiles, look});
+        wait(p1);
+        p1 = pair(t, slots, slots + kStride, Refill{rs, (t + 2u) * kStep + lo, l0, t + 2u < ntiles, look, kM0},
+                  Refill{rs, (t + 3u) * kStep + lo, l1, t + 3u < ntiles, look, kM0});
         if (p1 == ~0u) {
             vm_drain();
             return true;
         }
     }
     if (t < ntiles) {
-        vm_wait(p1);
-        if (single(t, slots, Refill{rs, 0u, l0, false, look}) == ~0u) {
+        wait(p1);
+        if (single(t, slots, Refill{rs, 0u, l0, false, look, kM0}) == ~0u) {
             vm_drain();
             return true;
         }

@@ -109,8 +109,9 @@ __global__ __launch_bounds__(kEncBlock) void encode_kernel(const uint8_t* __rest
     // tile's: loads complete in issue order, so walk_tiles' wait for tile 0 covers it (no tile, no
     // load: nothing may land in LDS after the wave ends)
     const u32* elut = elut_all + wid * kInsWaveWords;
+    constexpr u32 kLean = kWtMode == 1u ? kLeanEnc : 0u;   // (the small-batch instantiation: rle_device.h)
     if (U64 != 0u && !RLE_NOWALK && lane < kInsDmaLanes)
-        dma_tile(make_rsrc(&kEncInsLut, 4u * kInsWaveWords), 16u * lane, uniform(lds_addr(elut)));
+        dma_tile<false, (kLean & kLeanM0) != 0u>(make_rsrc(&kEncInsLut, 4u * kInsWaveWords), 16u * lane, uniform(lds_addr(elut)));
     const u32 U = (u32)U64;
     const u32x4 rsi = make_rsrc(src, (U + 15u) & ~15u);
     const u32x4 rso = make_rsrc(dst, U + U / 2u);
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(kEncBlock) void encode_kernel(const uint8_t* __rest
         // (enc_span_test) in the small-batch instantiation only (kWtMode 1: at most one residency
         // round): with it the kernel takes 75 VGPRs instead of 72, a wave per SIMD less on large
         // batches (16384 x 64 KiB encode +2.6 %, profiles/r7_items_ab.md)
-        walk_pairs<kEncStep, true>(rsi, 0u, RLE_NOWALK ? 0u : enc_ntiles_for(U), lane, slots,
+        walk_pairs<kEncStep, true, kLean>(rsi, 0u, RLE_NOWALK ? 0u : enc_ntiles_for(U), lane, slots,
                    [&](u32 t, const uint8_t* sa, const uint8_t* sb, const Refill& na, const Refill& nb) {
                        tl_mark(b, 2u + t, lane);
                        tl_mark(b, 3u + t, lane);
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(kEncBlock) void encode_kernel(const uint8_t* __rest
             tl_mark(b, 2u + t, lane);
             return enc_tile<false, true>(cs, nx, t * kTileStep, U, U, lane, stage, dst, rso, st, kc, elut);
         };
-        walk_tiles(rsi, 0u, RLE_NOWALK ? 0u : ntiles_for(U), lane, slots, tile);
+        walk_tiles<kTileStep, false, kLean & kLeanM0>(rsi, 0u, RLE_NOWALK ? 0u : ntiles_for(U), lane, slots, tile);
     }
     RLE_STAMP(st.sp, 6);   // drain
     // the final partial chunk (< 16 bytes, staging chunk 1): byte stores, nothing past C
@@ -280,25 +281,40 @@ __device__ __forceinline__ void walk_priority(u32 ntiles) {
 }
 // The prologue of decode_kernel and decode_packed_kernel, behind walk_prime.  The phase table and the
 // compaction selectors, shared by the workgroup: wave 0 LDS-DMAs them (2.3 KB) after every wave has
-// issued its first tiles' loads, waits for its own table loads (they complete in issue order, its
-// tile loads after them may still be in flight), and one barrier publishes them, normally before
-// the first tile's data has landed.  (At kernel start every wave's loads queue at once: one copy
+// issued its first tiles' loads, waits for all of its loads (the tables' complete last), and one
+// barrier publishes them.  (At kernel start every wave's loads queue at once: one copy
 // per workgroup instead of per wave keeps the table traffic off the first tiles' path.)  Every wave
 // zeroes its staging (kStageB bytes) meanwhile.
-template <u32 kStageB>
-__device__ __forceinline__ void dec_prologue(u32 wid, u32 lane, DecEntry* tbl, u32x4* clut, uint8_t* stage) {
+// kLean & kLeanTable (an A/B switch of decode_kernel<192, 0, 1>, measured slower and not taken:
+// 4 KiB zero decode +1.5 to +2.6 %): wave 0 issues the table loads ahead of its own
+// tiles' (dec_tables_dma before walk_prime) and waits for them alone, with a count that leaves its
+// tile loads in flight; the other three waves then wait at the barrier for the tables, not for wave
+// 0's second tile as well.
+template <bool kFreeM0>
+__device__ __forceinline__ void dec_tables_dma(u32 wid, u32 lane, DecEntry* tbl, u32x4* clut) {
     if (wid == 0u) {
         const u32x4 rt = make_rsrc(&kDecTable, (u32)sizeof(DecTable));
         const u32 lt = uniform(lds_addr(tbl));
         asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh
-        dma_tile(rt, 16u * lane, lt);
-        dma_tile(rt, 1024u + 16u * lane, lt + 1024u);
+        dma_tile<false, kFreeM0>(rt, 16u * lane, lt);
+        dma_tile<false, kFreeM0>(rt, 1024u + 16u * lane, lt + 1024u);
         if (lane < kCompactEntries)
-            dma_tile(make_rsrc(&kCompactLut, (u32)sizeof(DecCompactLut)), 16u * lane, uniform(lds_addr(clut)));
+            dma_tile<false, kFreeM0>(make_rsrc(&kCompactLut, (u32)sizeof(DecCompactLut)), 16u * lane, uniform(lds_addr(clut)));
     }
+}
+// ntiles: the wave's tile count (walk_prime loaded min(ntiles, 2) tiles)
+template <u32 kStageB, u32 kLean = 0u>
+__device__ __forceinline__ void dec_prologue(u32 wid, u32 lane, DecEntry* tbl, u32x4* clut, uint8_t* stage, u32 ntiles) {
+    constexpr bool kFirst = (kLean & kLeanTable) != 0u;
+    if (!kFirst) dec_tables_dma<(kLean & kLeanM0) != 0u>(wid, lane, tbl, clut);
     for (u32 k = lane; k < kStageB / 16u; k += kWave)
         reinterpret_cast<u32x4*>(stage)[k] = u32x4{0u, 0u, 0u, 0u};
-    if (wid == 0u) vm_drain();   // (its own tile loads were issued first: both are in)
+    if (wid == 0u) {
+        if (!kFirst) vm_drain();   // (its own tile loads were issued first: both are in)
+        else if (ntiles >= 2u) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   // (loads complete in issue order)
+        else if (ntiles == 1u) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+        else vm_drain();
+    }
     if (kDecWaves > 1) __syncthreads();
     else wave_lds_sync();
 }
@@ -370,9 +386,12 @@ __global__ __launch_bounds__(kDecBlock) void decode_kernel(const uint8_t* __rest
     if (kChunks >= 191u) walk_priority(ntiles);
     uint8_t* stage = stage_all + wid * kStageB;
     const uint8_t* slots = slots_all + wid * kDepth * kSlot;
-    walk_prime(rsi, 0u, ntiles, lane, slots);
+    // (the small-batch instantiation's shorter scalar stream: rle_device.h kLean)
+    constexpr u32 kLean = (kWtMode == 1u && kChunks >= 191u) ? kLeanDec : 0u;
+    if (kLean & kLeanTable) dec_tables_dma<(kLean & kLeanM0) != 0u>(wid, lane, tbl, clut);
+    walk_prime<kTileStep, false, kLean>(rsi, 0u, ntiles, lane, slots);
     tl_mark(b, 15, lane);   // (diagnostic builds: the first tiles' loads issued)
-    dec_prologue<kStageB>(wid, lane, tbl, clut, stage);
+    dec_prologue<kStageB, kLean>(wid, lane, tbl, clut, stage, ntiles);
 
     if (b < n) {
         if (bad) {
@@ -391,7 +410,7 @@ __global__ __launch_bounds__(kDecBlock) void decode_kernel(const uint8_t* __rest
             tl_mark(b, 2u + t, lane);
             return dec_tile<true, kChunks, true>(cs, nx, t * kTileStep, C, C, U, lane, tbl, stage, dst, rso, st, kc, clut);
         };
-        const bool serial = walk_tiles(rsi, 0u, ntiles, lane, slots, tile, true);
+        const bool serial = walk_tiles<kTileStep, false, kLean>(rsi, 0u, ntiles, lane, slots, tile, true);
         RLE_STAMP(st.sp, 7);   // drain after the last tile
         u32 stat = RLE_STATUS_OK;
         if (serial) stat = dec_serial(src, C, U, cap, dst, lane, stage, kStageB);
@@ -459,7 +478,7 @@ __global__ __launch_bounds__(kDecBlock) void decode_packed_kernel(const uint8_t*
     uint8_t* stage = stage_all + wid * kStageB;
     const uint8_t* slots = slots_all + wid * 2u * kSlot;
     walk_prime(rsi, 0u, ntiles, lane, slots);
-    dec_prologue<kStageB>(wid, lane, tbl, clut, stage);
+    dec_prologue<kStageB>(wid, lane, tbl, clut, stage, ntiles);
 
     if (b >= n) return;
     if (bad) {
