@@ -727,6 +727,15 @@ int rle_relocate_batch_device(const void* d_src, const uint64_t* d_off, const ui
  * victims' names, log EVICTED and notify waiting clients; the sizes, the keys and the tables never
  * leave the device.  After the eviction a victim's row of the caller's tables is dead: the relocation
  * gives it no slot (d_new_cap[i] = 0), and what a later append reports for it says nothing.
+ * The caller's duty for a dead row (a victim, or a file it removed), before the next batched call over the
+ * tables and after the gather has taken the victims' rows: d_len[i] = 0, d_ulen[i] = 0, d_tail[i] =
+ * RLE_TAIL_EMPTY (one masked multiply by d_keep on the device), and d_new_len[i] = 0 in every later batch.
+ * Every entry then reads nothing through the row's stale d_off (a zero length is no access: the scans
+ * answer tail 0, ulen 0, RLE_STATUS_OK, the size and fit entries d_need = 0, RLE_STATUS_OK, the relocation
+ * gives no slot), d_want, d_off and d_cap may stay whatever they were, and the row revived (d_live[i] = 1,
+ * a key) is the empty stream, which an append accepts.  A row left with its old d_len and d_tail is read
+ * at d_off[i] + t by the next size or fit call, and d_off[i] is by then the next file's offset or *d_total;
+ * with d_len zeroed but d_tail kept the row's first append after a revival is RLE_STATUS_NOTCANON.
  * On the host, checked in this order: a NULL d_victims, d_summary, tables_in or
  * tables_out, ntables of 0 or above 8, an unknown order, or a NULL table pointer is RLE_E_INVAL; then
  * cap == 0 is RLE_OK and launches nothing.

@@ -169,6 +169,47 @@ def test_keys_compare_unsigned():
     assert r.victims == [3, 1, 4, 0]
 
 
+# ---------------------------------------------------------------- wide keys, several files per thread
+# evict_model.random_store's five key kinds (heavy ties, timestamps, all 64 bits, top and bottom bytes,
+# shifted) at sizes where each of the 1024 threads holds two or five files, so the radix select runs
+# up to eight passes over keys that differ in their top bytes.  The seeds were picked on the CPU; the
+# first draw of random_store is the key kind.
+WIDE_SEEDS = {1500: (0, 1, 2, 3, 4, 5, 6, 7, 8, 9), 5000: (0, 1, 3, 4, 5, 12, 13, 17, 19, 20)}
+
+
+def wide_kind(n, seed):
+    return int(np.random.default_rng([n, seed]).integers(0, 5))
+
+
+def test_wide_key_seeds_draw_every_kind():
+    for n, seeds in WIDE_SEEDS.items():
+        assert {wide_kind(n, seed) for seed in seeds} == {0, 1, 2, 3, 4}, n
+
+
+@pytest.mark.parametrize("n,seed", [(n, seed) for n, seeds in WIDE_SEEDS.items() for seed in seeds])
+def test_wide_keys(n, seed):
+    s = M.random_store(np.random.default_rng([n, seed]), n)
+    kind = wide_kind(n, seed)
+    if kind == 2:
+        assert max(s["keys"]) >> 56 and len({k >> 56 for k in s["keys"]}) > 100    # the top byte differs
+    if kind == 3:
+        assert {k >> 56 for k in s["keys"]} == {0, 1, 2} == {k & 255 for k in s["keys"]}
+    Store(n).select(s)
+
+
+def test_global_sort_of_64_bit_keys():
+    """m > 4096 victims (the sort over d_victims in global memory) whose keys use all 64 bits and
+    differ in the top byte."""
+    n, m = 5000, 4500
+    rng = np.random.default_rng(64)
+    keys = [int(k) & M.M64 for k in rng.integers(0, 1 << 63, n) * 2 + rng.integers(0, 2, n)]
+    s = M.store(keys, [int(c) for c in rng.integers(0, 5000, n)], [int(c) for c in rng.integers(0, 6000, n)])
+    r = Store(n).select(with_count(s, m, by_files=True))
+    assert r.status == M.OK and len(r.victims) == m
+    assert len({keys[v] >> 56 for v in r.victims}) > 200
+    assert [keys[v] for v in r.victims] == sorted(keys[v] for v in r.victims)
+
+
 # ---------------------------------------------------------------- gather
 @pytest.fixture(scope="module")
 def selected():
