@@ -22,7 +22,6 @@
 // declines take the exact serial decoder, as there.
 #include "rle_coop_limits.h"
 #include "rle_device.h"
-#include "rle_service.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -53,14 +52,11 @@ __device__ __forceinline__ void coop_release(u32 flags) {
 // kW waves; 1024-byte tiles (enc_tile<true> form), so buffers of up to 1024 kW kR bytes are coop:
 // kR rounds of kW tiles, round r + 1's tiles loading (into the slots round r has read) while round
 // r writes its staging; the run start and output offset entering a round are carried from the last.
-// One buffer (b: its index in out_len / status).  kU (the resident small-call service,
-// rle_service.hip, whose workgroup serves one buffer after another): no wave ends before the last
-// barrier -- the waves without a tile idle through the barriers -- and all of them share the stores.
-template <u32 kW, bool kU, u32 kR = 1>
+// One buffer (b: its index in out_len / status).
+template <u32 kW, u32 kR = 1>
 __device__ __forceinline__ void enc_coop_body(const uint8_t* src, uint8_t* dst, uint64_t U64,
                                               uint64_t* __restrict__ out_len, uint32_t* __restrict__ status, u32 b,
                                               u32 wt) {
-    static_assert(kR == 1u || !kU, "the service serves one round");
     constexpr u32 kUmax = kEncStep * kW * kR;
     // output position r at byte 16 + r (chunk 0: guard of the non-starts' back-writes); +32: the
     // writes of positions past U land at the output end
@@ -105,7 +101,7 @@ __device__ __forceinline__ void enc_coop_body(const uint8_t* src, uint8_t* dst, 
     }
     // waves with a tile in the first round (wave 0 also for U = 0)
     const u32 nact = ntiles == 0u ? 1u : (ntiles < kW ? ntiles : kW);
-    if (!kU && wid >= nact) return;   // ended waves do not hold up s_barrier
+    if (wid >= nact) return;   // ended waves do not hold up s_barrier
     const u32 nrounds = kR == 1u || ntiles == 0u ? 1u : (ntiles + kW - 1u) / kW;
     const uint8_t* slot = slots + wid * kEncSlot;
     asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh (walk_prime)
@@ -185,7 +181,7 @@ __device__ __forceinline__ void enc_coop_body(const uint8_t* src, uint8_t* dst, 
     __syncthreads();
     // store: whole 16-byte chunks, then the final partial chunk byte by byte (nothing past C)
     const u32 total = O_c;
-    const u32 nthr = kWave * (kU ? kW : nact), t = threadIdx.x, nfull = total >> 4;
+    const u32 nthr = kWave * nact, t = threadIdx.x, nfull = total >> 4;
     for (u32 c = t; c < nfull; c += nthr)
         vstore(rso, 16u * c, *reinterpret_cast<const u32x4*>(stage + 16u + 16u * c), (wt & kLaunchWt) != 0u);
     if (t < (total & 15u)) dst[16u * nfull + t] = stage[16u + 16u * nfull + t];
@@ -205,169 +201,21 @@ __global__ __launch_bounds__(kWave* kW) void enc_coop_kernel(const uint8_t* __re
                                                              uint32_t* __restrict__ status, uint32_t n, uint32_t wt) {
     const u32 b = blockIdx.x;
     if (b >= n) return;
-    enc_coop_body<kW, false, kR>(in + in_off[b], out + out_off[b], in_len[b], out_len, status, b, wt);
+    enc_coop_body<kW, kR>(in + in_off[b], out + out_off[b], in_len[b], out_len, status, b, wt);
 }
-
-// ---------------------------------------------------------------- encode, any size, one pass
-// (round 5, measured no faster than the segmented encode on 1 MiB buffers and slower on zero-filled
-// ones, DESIGN.md §4: in the RLE_VARIANTS test library only)
-#if RLE_VARIANTS
-// One workgroup of kW waves walks a whole buffer in rounds of kW tiles (enc_coop_body's rounds),
-// reading each input byte once: a round's output is staged, its whole 16-byte chunks stored, and
-// the partial chunk carried to the staging's front for the next round.  The staging holds one
-// round's output (at most 1.5 x 1024 kW bytes) past the carried chunk, so any buffer size fits.
-// Thread 0 stores chunk 0 and then moves the partial chunk onto it (no other thread reads chunk 0
-// or writes the partial chunk in that phase), so a round has four barriers.
-template <u32 kW>
-__device__ __forceinline__ void enc_stream_body(const uint8_t* src, uint8_t* dst, uint64_t U64,
-                                                uint64_t* __restrict__ out_len, uint32_t* __restrict__ status, u32 b,
-                                                u32 wt) {
-    constexpr u32 kRoundOut = kEncStep * kW + kEncStep * kW / 2u;
-    constexpr u32 kStage = (16u + 16u + kRoundOut + 32u + 127u) & ~127u;
-    __shared__ __attribute__((aligned(16))) uint8_t slots[kW * kEncSlot];
-    __shared__ __attribute__((aligned(128))) uint8_t stage[kStage];
-    __shared__ u32 xch[2 * kW];
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = coop_wave();
-    u32 bad = (((uintptr_t)src | (uintptr_t)dst) & 15u) ? RLE_STATUS_MISALIGNED : 0u;
-    if (U64 > kMaxBufferBytes) bad |= RLE_STATUS_TOOLARGE;
-    if (bad) {
-        if (threadIdx.x == 0) {
-            out_len[b] = 0;
-            put_status(status, b, bad, wt);
-        }
-        return;
-    }
-    const u32 U = (u32)U64;
-    const u32x4 rsi = make_rsrc(src, (U + 15u) & ~15u);
-    const u32x4 rso = make_rsrc(dst, U + U / 2u);
-    const EncK kc = enc_k();
-    const bool wtb = (wt & kLaunchWt) != 0u;
-    const u32 ntiles = enc_ntiles_for(U);
-    const u32 nact = ntiles == 0u ? 1u : (ntiles < kW ? ntiles : kW);
-    if (wid >= nact) return;   // ended waves do not hold up s_barrier
-    const u32 nthr = kWave * nact;
-    const u32 nrounds = ntiles == 0u ? 1u : (ntiles + kW - 1u) / kW;
-    const uint8_t* slot = slots + wid * kEncSlot;
-    asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh (walk_prime)
-    if (wid < ntiles) Refill{rsi, kEncStep * wid + 16u * lane, uniform(lds_addr(slot)), true, lane == 0u}();
-    // carried: run start, output offset, last input byte; base = output offset of staging byte 16
-    u32 rs_c = 0u, O_c = 0u, top_c = 0u, base = 0u;
-    u32 nst = 0u;   // store instructions this wave issued after the round's tile loads (the last round)
-    for (u32 r = 0; r < nrounds; ++r) {
-        const u32 t = r * kW + wid;
-        const bool act = t < ntiles;
-        const u32 rtiles = ntiles - r * kW < kW ? ntiles - r * kW : kW;
-        vm_wait_deep(nst);   // the tile loads, not the stores issued after them (vmcnt is in order)
-        __syncthreads();   // the round's tiles have landed; the carried chunk is in place
-        EncAn an{};
-        if (act) {
-            const u32x4 cur = *reinterpret_cast<const u32x4*>(slot + 16u * lane);
-            const uint2 look = *reinterpret_cast<const uint2*>(slot + kSlot);
-            const u32 prev_top = wid ? *reinterpret_cast<const u32*>(slot - kEncSlot + kSlot - 4u) & 0xFF000000u : top_c;
-            an = enc_analyze_bounds<true>(cur, look, kEncStep * t, U, U, lane, prev_top, kc);
-            if (lane == 0) xch[wid] = readlane(an.incl, kWave - 1u);
-        }
-        if (r + 1u < nrounds)
-            top_c = *reinterpret_cast<const u32*>(slots + (kW - 1u) * kEncSlot + kSlot - 4u) & 0xFF000000u;
-        __syncthreads();   // every slot read: the next round's tiles may land
-        if (t + kW < ntiles) Refill{rsi, kEncStep * (t + kW) + 16u * lane, uniform(lds_addr(slot)), true, lane == 0u}();
-        u32 nout = 0u, oincl = 0u;
-        if (act) {
-            u32 rs = rs_c;
-            for (u32 s = 0; s < wid; ++s) rs = xch[s] > rs ? xch[s] : rs;
-            enc_tokens(an, rs);
-            nout = bcnt(an.P, bcnt(an.P, bcnt(an.T, 0u)));
-            oincl = wave_scan_incl(nout, 0u, OpAdd());
-            if (lane == 0) xch[kW + wid] = readlane(oincl, kWave - 1u);
-        }
-        __syncthreads();
-        u32 O = O_c, rtot = 0u, rmax = rs_c;
-        for (u32 s = 0; s < rtiles; ++s) {
-            const u32 c = xch[kW + s];
-            O += s < wid ? c : 0u;
-            rtot += c;
-            rmax = xch[s] > rmax ? xch[s] : rmax;
-        }
-        if (act) {
-            const u32* w = an.w;
-            const u32 T = an.T, P = an.P, B24 = an.B24, validm = an.validm;
-            const u32 NS = validm & ~T;
-            const u32 obase = 16u + (O - base) + oincl - nout;
-            const u32 e0 = lds_addr(stage) + obase;
-            if (kEncStep * t + kEncStep <= U) enc_pass1<true>(w, T, P, NS, e0, kc.V01);
-            else enc_pass1<false>(w, T, P, NS, e0, 0u);
-            u32 prem = P;
-            while (__builtin_amdgcn_ballot_w64(prem != 0u)) {
-                if (prem) {
-                    const u32 j = (u32)__builtin_ctz(prem);
-                    prem &= prem - 1u;
-                    const u32 mj = lowmask(j);
-                    const u32 oj = bcnt(P & mj, bcnt(P & mj, bcnt(T & mj, obase)));
-                    stage[oj + 2u] = (uint8_t)('1' + (u32)__builtin_ctz((B24 >> (j + 1u)) | 0x100u));
-                }
-            }
-            const u32 vnext = (validm >> 1) | ((from_next_lane(validm, 0u) & 1u) << 15);
-            const u32 PX = P & ~vnext;
-            if (__builtin_amdgcn_ballot_w64(PX != 0u)) {
-                if (PX) {
-                    const u32 j = (u32)__builtin_ctz(PX);
-                    const u32 mj = lowmask(j);
-                    const u32 oj = bcnt(P & mj, bcnt(P & mj, bcnt(T & mj, obase)));
-                    const u32 wj = j < 4u ? w[0] : j < 8u ? w[1] : j < 12u ? w[2] : w[3];
-                    stage[oj + 1u] = (uint8_t)(wj >> (8u * (j & 3u)));
-                }
-            }
-        }
-        O_c += rtot;
-        rs_c = rmax;
-        __syncthreads();   // the round's output is staged
-        // whole chunks of [base, O_c) out; the partial one to the front (thread 0, after chunk 0)
-        const u32 nfull = (O_c - base) >> 4;
-        for (u32 c = threadIdx.x; c < nfull; c += nthr)
-            vstore(rso, base + 16u * c, *reinterpret_cast<const u32x4*>(stage + 16u + 16u * c), wtb);
-        if (threadIdx.x == 0u && nfull)
-            *reinterpret_cast<u32x4*>(stage + 16u) = *reinterpret_cast<const u32x4*>(stage + 16u + 16u * nfull);
-        base += 16u * nfull;
-        const u32 w0 = kWave * wid;
-        nst = uniform(nfull > w0 ? (nfull - w0 + nthr - 1u) / nthr : 0u);
-    }
-    __syncthreads();
-    const u32 total = O_c;
-    if (threadIdx.x < total - base) dst[base + threadIdx.x] = stage[16u + threadIdx.x];
-    coop_release(wt);
-    if (threadIdx.x == 0) {
-        out_len[b] = total;
-        put_status(status, b, RLE_STATUS_OK, wt);
-    }
-}
-template <u32 kW>
-__global__ __launch_bounds__(kWave* kW) void enc_stream_kernel(const uint8_t* __restrict__ in,
-                                                               const uint64_t* __restrict__ in_off,
-                                                               const uint64_t* __restrict__ in_len,
-                                                               uint8_t* __restrict__ out,
-                                                               const uint64_t* __restrict__ out_off,
-                                                               uint64_t* __restrict__ out_len,
-                                                               uint32_t* __restrict__ status, uint32_t n, uint32_t wt) {
-    const u32 b = blockIdx.x;
-    if (b >= n) return;
-    enc_stream_body<kW>(in + in_off[b], out + out_off[b], in_len[b], out_len, status, b, wt);
-}
-#endif  // RLE_VARIANTS (one-pass encode)
 
 // ================================================================ DECODE
 // kW waves (tiles of 1008 bytes: dec_tile's geometry); buffers decoding to at most kUmax bytes from
 // at most kR kW tiles: kR rounds of kW tiles as in enc_coop_body, the token phase and output offset
 // carried across rounds, every round scattering into the one staging; then the fill and the stores.
-// One buffer (b: its index in status; kU as enc_coop_body).
-template <u32 kW, u32 kUmax, bool kU, u32 kR = 1>
+// One buffer (b: its index in status).
+template <u32 kW, u32 kUmax, u32 kR = 1>
 __device__ __forceinline__ void dec_coop_body(const uint8_t* src, uint8_t* dst, uint64_t C64, uint64_t U64,
                                               uint64_t cap, uint32_t* __restrict__ status, u32 b, u32 wt) {
     // decoded position r at u16 16 + r (dec_tile's staging, one for the whole buffer); the one-wave
     // fallback needs kDecStage
     constexpr u32 kStageC = 2u * (16u + kUmax + 32u);
     constexpr u32 kStage = ((kStageC > kDecStage ? kStageC : kDecStage) + 127u) & ~127u;
-    static_assert(kR == 1u || !kU, "the service serves one round");
     constexpr u32 kChunks = (kUmax + 15u) / 16u;
     constexpr u32 kSlotsB = (kW > 2u ? kW : 2u) * kSlot;
     // the fill's chunk-to-chunk bytes: in the slots (free by then) when they fit, which keeps the
@@ -415,8 +263,8 @@ __device__ __forceinline__ void dec_coop_body(const uint8_t* src, uint8_t* dst, 
     }
     // waves with a tile in the first round (wave 0 also for C = 0)
     const u32 nact = ntiles == 0u ? 1u : (ntiles < kW ? ntiles : kW);
-    if (!kU && wid >= nact) return;   // ended waves do not hold up s_barrier
-    const u32 nthr = kWave * (kU ? kW : nact);   // threads zeroing, filling and storing
+    if (wid >= nact) return;   // ended waves do not hold up s_barrier
+    const u32 nthr = kWave * nact;   // threads zeroing, filling and storing
     const u32 nrounds = kR == 1u || ntiles == 0u ? 1u : (ntiles + kW - 1u) / kW;
     const uint8_t* slot = slots + wid * kSlot;
     asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh (walk_prime)
@@ -533,7 +381,7 @@ __global__ __launch_bounds__(kWave* kW) void dec_coop_kernel(const uint8_t* __re
     const u32 b = blockIdx.x;
     if (b >= n) return;
     const uint64_t* capp = out_cap ? out_cap : out_len;
-    dec_coop_body<kW, kUmax, false, kR>(in + in_off[b], out + out_off[b], in_len[b], out_len[b], capp[b], status, b, wt);
+    dec_coop_body<kW, kUmax, kR>(in + in_off[b], out + out_off[b], in_len[b], out_len[b], capp[b], status, b, wt);
 }
 
 // One buffer whose sizes the host knows (the drop-in's zero-copy calls, round 6): the same bodies
@@ -544,88 +392,15 @@ __global__ __launch_bounds__(kWave* kW) void enc_coop_one_kernel(const uint8_t* 
                                                                  uint8_t* __restrict__ dst, uint64_t U,
                                                                  uint64_t* __restrict__ out_len,
                                                                  uint32_t* __restrict__ status, uint32_t wt) {
-    enc_coop_body<kW, false, kR>(src, dst, U, out_len, status, 0u, wt);
+    enc_coop_body<kW, kR>(src, dst, U, out_len, status, 0u, wt);
 }
 template <u32 kW, u32 kUmax, u32 kR = 1>
 __global__ __launch_bounds__(kWave* kW) void dec_coop_one_kernel(const uint8_t* __restrict__ src,
                                                                  uint8_t* __restrict__ dst, uint64_t C, uint64_t U,
                                                                  uint64_t cap, uint32_t* __restrict__ status,
                                                                  uint32_t wt) {
-    dec_coop_body<kW, kUmax, false, kR>(src, dst, C, U, cap, status, 0u, wt);
+    dec_coop_body<kW, kUmax, kR>(src, dst, C, U, cap, status, 0u, wt);
 }
-
-#if RLE_VARIANTS   // the resident service is built into the test library only (round 5)
-// ================================================================ resident small-call service
-// (rle_service.h): one workgroup per drop-in thread context.  Wave 0 polls the context's mailbox
-// line (lanes 0..15: one 64-byte read over PCIe with system-scope loads; an acquire fence once a
-// request is seen);
-// a new complete request (req != done, tail == req) is broadcast through LDS and served by all
-// kSvcWaves waves with the barrier-uniform codec bodies on the context's mapped buffer; every wave
-// waits for its stores, and after a barrier thread 0 releases them at system scope and stores the
-// acknowledgement.  kSvcIdleUs after the last request, kSvcLifeUs after the launch, on the stop
-// word, or after kSvcMaxPolls polls, thread 0 marks `gone` with the launch's generation and the
-// workgroup ends.  Mailbox words are read only with vector loads (never the scalar cache).
-constexpr u32 kSvcUmax = 16384;
-constexpr u32 kSvcMaxPolls = 1u << 24;
-__global__ __launch_bounds__(kWave* kSvcWaves) void svc_kernel(SvcMail* mb, const uint8_t* src, uint8_t* dst,
-                                                              uint32_t gen, uint32_t done, uint64_t idle_ticks,
-                                                              uint64_t life_ticks) {
-    __shared__ u32 sh[8];   // 0: action (0 none, 1 serve, 2 exit); 1..7: words 1..7 of the line (7: tail = req)
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = coop_wave();
-    const uint64_t t0 = wall_clock64();
-    uint64_t last = t0;
-    const uint32_t* line = reinterpret_cast<const uint32_t*>(&mb->r);
-    for (u32 polls = 0;; ++polls) {
-        if (wid == 0u) {
-            const u32 w = lane < 16u ? __hip_atomic_load(line + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
-            const u32 req = readlane(w, 0), tail = readlane(w, 7), stop = readlane(w, 6);
-            const uint64_t now = wall_clock64();
-            u32 act = 0u;
-            u32 wl = w;
-            if (req != done && tail == req) {
-                // acquire once per request, not per poll (a system-scope acquire invalidates the
-                // XCD's L2: per poll, 8 resident workgroups slowed every other's request, r4f)
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-                act = 1u;
-                last = now;
-                // the line again, ordered after seeing its new sequence number: the host writes the
-                // fields before `tail` and `req`, but the lanes' loads of one poll are not ordered
-                // among themselves, so a field read by another lane may predate them
-                wl = lane < 8u ? __hip_atomic_load(line + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
-            } else if (stop || now - last > idle_ticks || now - t0 > life_ticks || polls > kSvcMaxPolls) {
-                act = 2u;
-            }
-            if (lane < 8u) sh[lane] = lane == 0u ? act : wl;
-            if (act == 1u) done = req;
-        }
-        __syncthreads();
-        const u32 act = uniform(sh[0]);
-        if (act == 2u) {
-            if (threadIdx.x == 0) __hip_atomic_store(&mb->a.gone, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            return;
-        }
-        if (act == 1u) {
-            const u32 seq = uniform(sh[7]), op = uniform(sh[1]), in_len = uniform(sh[2]);
-            const u32 out_len = uniform(sh[3]), cap = uniform(sh[4]), wt = uniform(sh[5]) & kLaunchWt;
-            if (op == kSvcEncode) {
-                enc_coop_body<kSvcWaves, true>(src, dst, in_len, &mb->a.res_len, &mb->a.status, 0u, wt);
-            } else {
-                dec_coop_body<kSvcWaves, kSvcUmax, true>(src, dst, in_len, out_len, cap, &mb->a.status, 0u, wt);
-            }
-            vm_drain();   // this wave's stores acknowledged (in the L2 or past it) ...
-            __syncthreads();
-            if (threadIdx.x == 0) {   // ... then one system-scope release of them all and the acknowledgement
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-                __hip_atomic_store(&mb->a.ack, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        } else {
-            __syncthreads();   // (wave 0 rewrites sh at the next poll)
-            __builtin_amdgcn_s_sleep(2);
-        }
-    }
-}
-#endif  // RLE_VARIANTS
 
 }  // namespace rle
 
@@ -801,60 +576,9 @@ extern "C" int rle_mi355x_coop_form(int decode, uint64_t max_in_len, uint64_t ma
     return w != 0u;
 }
 
-#if RLE_VARIANTS
-namespace {
-std::atomic<int> g_stream_waves{0};   // 0: from RLE_MI355X_STREAM_WAVES at the first launch
-}
-// Tests: waves per workgroup of the one-pass kernels (4, 8 or 16).
-extern "C" int rle_mi355x_set_stream_waves(int w) {
-    if (w != 4 && w != 8 && w != 16) return RLE_E_INVAL;
-    g_stream_waves.store(w, std::memory_order_relaxed);
-    return RLE_OK;
-}
-// One workgroup per buffer over the whole buffer (enc_stream_body), any size: RLE_OK if launched.
-// RLE_MI355X_STREAM_WAVES (8 or 16, default 16): waves per workgroup.
-extern "C" int rle_encode_stream_launch(const void* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len, void* d_out,
-                                        const uint64_t* d_out_off, uint64_t* d_out_len, uint32_t* d_status, uint32_t n,
-                                        uint32_t flags, void* stream) {
-    if (n == 0) return RLE_OK;
-    if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len) return RLE_E_INVAL;
-    const hipStream_t s = (hipStream_t)stream;
-    const uint32_t wt = coop_store_policy(n) | flags;
-    if (g_stream_waves.load(std::memory_order_relaxed) == 0) {
-        const char* e = getenv("RLE_MI355X_STREAM_WAVES");
-        g_stream_waves.store(e && atoi(e) == 8 ? 8 : 16, std::memory_order_relaxed);
-    }
-    if (g_stream_waves.load(std::memory_order_relaxed) == 4)
-        hipLaunchKernelGGL(rle::enc_stream_kernel<4>, dim3(n), dim3(64 * 4), 0, s, (const uint8_t*)d_in, d_in_off,
-                           d_in_len, (uint8_t*)d_out, d_out_off, d_out_len, d_status, n, wt);
-    else if (g_stream_waves.load(std::memory_order_relaxed) == 8)
-        hipLaunchKernelGGL(rle::enc_stream_kernel<8>, dim3(n), dim3(64 * 8), 0, s, (const uint8_t*)d_in, d_in_off,
-                           d_in_len, (uint8_t*)d_out, d_out_off, d_out_len, d_status, n, wt);
-    else
-        hipLaunchKernelGGL(rle::enc_stream_kernel<16>, dim3(n), dim3(64 * 16), 0, s, (const uint8_t*)d_in, d_in_off,
-                           d_in_len, (uint8_t*)d_out, d_out_off, d_out_len, d_status, n, wt);
-    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
-}
-#endif
-
 // Tests: switch the cooperative mode in-process (0 never, 1 always, -1 residency-gated default).
 extern "C" int rle_mi355x_set_coop_mode(int mode) {
     if (mode < -1 || mode > 1) return RLE_E_INVAL;
     g_coop_mode.store(mode, std::memory_order_relaxed);
     return RLE_OK;
 }
-
-#if RLE_VARIANTS
-// The resident small-call service of one drop-in thread context (rle_service.h; launched by
-// csrc/rle_dropin.cpp svc_ensure): one workgroup of kSvcWaves waves on the given stream, serving
-// requests on the context's mapped buffer (d_src: input, d_dst: output) from sequence `done` on.
-extern "C" int rle_service_launch(void* d_mail, const void* d_src, void* d_dst, uint32_t gen, uint32_t done,
-                                  void* stream) {
-    if (!d_mail || !d_src || !d_dst) return RLE_E_INVAL;
-    const uint64_t tick_per_us = 100;   // wall_clock64: 100 MHz
-    hipLaunchKernelGGL(rle::svc_kernel, dim3(1), dim3(rle::kWave * rle::kSvcWaves), 0, (hipStream_t)stream,
-                       (rle::SvcMail*)d_mail, (const uint8_t*)d_src, (uint8_t*)d_dst, gen, done,
-                       tick_per_us * rle::kSvcIdleUs, tick_per_us * rle::kSvcLifeUs);
-    return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
-}
-#endif  // RLE_VARIANTS

@@ -251,23 +251,6 @@ __device__ __forceinline__ void vm_wait_low(u32 n) {
         : "memory", "scc");
     if (n > 3u) vm_wait(n);
 }
-// the same for the walks whose counts reach past 15 (enc_stream_body)
-#define RLE_VMW2(N)                                           \
-    case N:                                                   \
-        asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); \
-        break;
-__device__ __forceinline__ void vm_wait_deep(u32 n) {
-    n = uniform(n);
-    switch (n < 39u ? n : 39u) {
-        RLE_VMW2(0) RLE_VMW2(1) RLE_VMW2(2) RLE_VMW2(3) RLE_VMW2(4) RLE_VMW2(5) RLE_VMW2(6) RLE_VMW2(7)
-        RLE_VMW2(8) RLE_VMW2(9) RLE_VMW2(10) RLE_VMW2(11) RLE_VMW2(12) RLE_VMW2(13) RLE_VMW2(14) RLE_VMW2(15)
-        RLE_VMW2(16) RLE_VMW2(17) RLE_VMW2(18) RLE_VMW2(19) RLE_VMW2(20) RLE_VMW2(21) RLE_VMW2(22) RLE_VMW2(23)
-        RLE_VMW2(24) RLE_VMW2(25) RLE_VMW2(26) RLE_VMW2(27) RLE_VMW2(28) RLE_VMW2(29) RLE_VMW2(30) RLE_VMW2(31)
-        RLE_VMW2(32) RLE_VMW2(33) RLE_VMW2(34) RLE_VMW2(35) RLE_VMW2(36) RLE_VMW2(37) RLE_VMW2(38) RLE_VMW2(39)
-        default: break;
-    }
-}
-#undef RLE_VMW2
 __device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // Launch flags, the kernels' `wt` argument: bit 0 write-through output stores (vstore), bit 1 the

@@ -41,13 +41,8 @@
 #include "rleCompression.h"
 #include "rle_fileops.h"
 #include "rle_mi355x.h"
-#include "rle_service.h"
 #include "rle_build.h"
 #include "rle_route.h"
-
-// Measured-slower host-path variants (call coalescing, pipelined staging) are compiled only into the
-// test library (build/librle_mi355x_testhooks.so) and `make variant` builds, never into the product
-// librle_mi355x.so (the measurements are in DESIGN.md §6).
 
 namespace {
 
@@ -64,7 +59,6 @@ struct Stats {
     std::atomic<uint64_t> bytes_in{0}, bytes_out{0};        // caller bytes in / returned bytes out
     std::atomic<uint64_t> bytes_h2d{0}, bytes_d2h{0};
     std::atomic<uint64_t> ns_stage_in{0}, ns_device{0}, ns_stage_out{0};
-    std::atomic<uint64_t> calls_coalesced{0}, launches_coalesced{0};   // zero-copy calls / their combined launches
     std::atomic<uint64_t> calls_registered{0}, calls_reg_fallback{0};  // registered large calls / staged instead
     std::atomic<uint64_t> calls_append_spliced{0};   // appends that kept the old stream up to its final token
 
@@ -144,15 +138,14 @@ rle::Settings g_set;
 
 // Host<->device transfers of large calls, selected by RLE_MI355X_STAGING:
 //   direct (default) the HIP runtime copies from / to the caller's pageable memory itself;
-//   pinned one memcpy into / out of this thread's pinned staging, one DMA;
-//   pipe   the pinned staging in chunks, the memcpy of one chunk overlapping the DMA of the next.
-// Calls below kPipeMinBytes always take "pinned" (one DMA each way).  Measured on MI355X
-// (profiles/r1d_staging.md): at 4 MiB, direct takes 231 / 255 us per compress / decompress call,
-// pinned 424 / 470, pipe 489 / 567; from 64 KiB to 1 MiB the three are within a few percent.
-enum class Staging { Pinned, Pipe, Direct };
+//   pinned one memcpy into / out of this thread's pinned staging, one DMA.
+// Calls below kDirectMinBytes always take "pinned".  Measured on MI355X (profiles/r1d_staging.md): at
+// 4 MiB, direct takes 231 / 255 us per compress / decompress call, pinned 424 / 470 (and the pinned
+// staging in overlapped chunks, since retired, 489 / 567); from 64 KiB to 1 MiB they are within a few
+// percent.
+enum class Staging { Pinned, Direct };
 Staging g_staging = Staging::Direct;
-constexpr size_t kPipeMinBytes = 256u << 10;
-constexpr int kPipeEvents = 16;
+constexpr size_t kDirectMinBytes = 256u << 10;
 
 size_t g_presize = 1u << 20;   // staging allocated with each thread context (presize); RLE_MI355X_PRESIZE
 // Zero-copy calls learn of their completion from the status word the kernel stores last, behind a
@@ -315,7 +308,6 @@ struct Ctx {
     int dev = 0;
     uint8_t* h_zc = nullptr;                         // mapped pinned buffer of the zero-copy calls
     uint8_t* d_zc = nullptr;                         // its device address
-    hipEvent_t ev[kPipeEvents] = {};                 // chunk completion events of the pipelined D2H
     hipStream_t s = nullptr;
     uint8_t* h_in = nullptr;  size_t h_in_cap = 0;    // pinned staging: caller bytes -> device
     uint8_t* h_out = nullptr; size_t h_out_cap = 0;   // pinned staging: device -> caller block
@@ -327,15 +319,7 @@ struct Ctx {
     uint8_t* d_mid = nullptr; size_t d_mid_cap = 0;   // RLEappend: decoded old content ‖ new bytes
     uint8_t* h_bm = nullptr;  size_t h_bm_cap = 0;    // RLEdecompressN: per-file offsets/lengths/status
     uint8_t* d_bm = nullptr;  size_t d_bm_cap = 0;
-    uint8_t* h_cw = nullptr;                         // mapped launch words of combined launches (submit)
-    uint8_t* d_cw = nullptr;
     uint32_t polled = 0;                             // polled launches since the last stream synchronize
-    int svc = -2;                                    // resident service (rle_service.h): 1 on, -1 off, -2 not yet asked
-    rle::SvcMail* svc_h = nullptr;                   // its mailbox (in the mapped zero-copy buffer) ...
-    rle::SvcMail* svc_d = nullptr;                   // ... and the mailbox's device address
-    hipStream_t svc_s = nullptr;                     // the service's stream
-    uint32_t svc_seq = 0;                            // latest request
-    uint32_t svc_gen = 0;                            // latest launch (0: none)
     bool full = false;                               // presized and warmed for large calls (preinit)
 };
 // h_meta / d_meta regions, one per launch that can be in flight on the stream at once:
@@ -350,12 +334,8 @@ constexpr size_t kMetaDec = 0, kMetaEnc = 8, kMetaApp = 16, kMetaSlots = 24;
 pthread_mutex_t g_exit_lock = PTHREAD_MUTEX_INITIALIZER;
 bool g_exiting = false;
 void preinit_join();   // below
-void svc_stop();   // below
-void svc_end(Ctx* c);
-void svc_unregister(Ctx* c);
 void on_exit_handler() {
     preinit_join();   // (when called from the start-up thread's own exit: never; it makes no exit call)
-    svc_stop();
     pthread_mutex_lock(&g_exit_lock);
     g_exiting = true;
     pthread_mutex_unlock(&g_exit_lock);
@@ -375,23 +355,18 @@ void free_ctx(void* p) {
         return;
     }
     (void)hipSetDevice(c->dev);
-    svc_end(c);
-    svc_unregister(c);
     if (c->s) (void)hipStreamSynchronize(c->s);
     (void)hipHostFree(c->h_in);
     (void)hipHostFree(c->h_out);
     (void)hipHostFree(c->h_meta);
     (void)hipHostFree(c->h_bm);
     (void)hipHostFree(c->h_zc);
-    (void)hipHostFree(c->h_cw);
     (void)hipFree(c->d_in);
     (void)hipFree(c->d_out);
     (void)hipFree(c->d_meta);
     (void)hipFree(c->d_ws);
     (void)hipFree(c->d_mid);
     (void)hipFree(c->d_bm);
-    for (hipEvent_t e : c->ev)
-        if (e) (void)hipEventDestroy(e);
     if (c->s) {
         (void)rle_decode_release_stream(c->s);   // (the issue-order array of large RLEdecompressN batches)
         (void)hipStreamDestroy(c->s);
@@ -412,18 +387,12 @@ void init_once() {
     if (const char* e = getenv("RLE_MI355X_SMALL")) g_set.zerocopy = strcmp(e, "copy") != 0;
     if (const char* e = getenv("RLE_MI355X_POLL")) g_poll = strcmp(e, "0") != 0;
     if (const char* e = getenv("RLE_MI355X_SPIN_NS")) g_spin_ns = strtoull(e, nullptr, 10);
-    if (const char* e = getenv("RLE_MI355X_SERVICE")) g_set.service = strcmp(e, "0") != 0;
     if (const char* e = getenv("RLE_MI355X_ZC_SEG")) g_set.zc_seg = (size_t)strtoull(e, nullptr, 10);
     if (const char* e = getenv("RLE_MI355X_ZC_COOP")) g_set.zc_coop = strcmp(e, "0") != 0;
     if (const char* e = getenv("RLE_MI355X_COOP")) g_set.zc_coop = g_set.zc_coop && strcmp(e, "0") != 0;   // (no workgroups to take them)
-#if RLE_VARIANTS
-    if (const char* e = getenv("RLE_MI355X_COALESCE")) g_set.coalesce = strcmp(e, "0") != 0;
-#endif
     if (const char* e = getenv("RLE_MI355X_PRESIZE")) g_presize = (size_t)strtoull(e, nullptr, 10);
-    if (const char* e = getenv("RLE_MI355X_STAGING")) {
+    if (const char* e = getenv("RLE_MI355X_STAGING"))
         if (!strcmp(e, "pinned")) g_staging = Staging::Pinned;
-        else if (RLE_VARIANTS && !strcmp(e, "pipe")) g_staging = Staging::Pipe;
-    }
 #if RLE_TEST_HOOKS
     if (const char* e = getenv("RLE_MI355X_FAIL_ALLOC_ABOVE")) g_fail_above = (size_t)strtoull(e, nullptr, 10);
 #endif
@@ -855,16 +824,9 @@ void finish_decode_tail(uint32_t st, char* r, size_t U, size_t E, FetchTail&& fe
     if (st & RLE_STATUS_OVERFLOW) warn_overflow("RLEdecompress");
 }
 
-// Chunk size of the pipelined transfers: at least 256 KiB, at most kPipeEvents chunks.
-size_t pipe_chunk(size_t n) {
-    size_t ch = 256u << 10;
-    while ((n + ch - 1) / ch > (size_t)kPipeEvents) ch *= 2;
-    return ch;
-}
-
 // Whether to_device copies n bytes through the pinned staging (else straight from the caller).
 bool direct(const void* p, size_t n) {
-    return g_staging == Staging::Direct && n >= kPipeMinBytes && !live_pages(p, n);
+    return g_staging == Staging::Direct && n >= kDirectMinBytes && !live_pages(p, n);
 }
 bool staged(const void* p, size_t n) { return n > 0 && !direct(p, n); }
 
@@ -879,12 +841,8 @@ void to_device(Ctx* c, uint8_t* d_dst, const void* src, size_t n, size_t hoff = 
     }
     grow_host(c->h_in, c->h_in_cap, hoff + n);
     uint8_t* h = c->h_in + hoff;
-    const size_t ch = (g_staging == Staging::Pipe && n >= kPipeMinBytes) ? pipe_chunk(n) : n;
-    for (size_t off = 0; off < n; off += ch) {
-        const size_t len = n - off < ch ? n - off : ch;
-        memcpy(h + off, p + off, len);
-        check(hipMemcpyAsync(d_dst + off, h + off, len, hipMemcpyHostToDevice, c->s), "H2D");
-    }
+    memcpy(h, p, n);
+    check(hipMemcpyAsync(d_dst, h, n, hipMemcpyHostToDevice, c->s), "H2D");
 }
 
 // Copies n device bytes at d_src (after everything queued on c->s) into the caller's dst; returns
@@ -901,26 +859,9 @@ void from_device(Ctx* c, void* dst, const uint8_t* d_src, size_t n) {
         return;
     }
     grow_host(c->h_out, c->h_out_cap, n);
-    if (g_staging != Staging::Pipe || n < kPipeMinBytes) {
-        check(hipMemcpyAsync(c->h_out, d_src, n, hipMemcpyDeviceToHost, c->s), "D2H");
-        check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-        memcpy(q, c->h_out, n);
-        return;
-    }
-    const size_t ch = pipe_chunk(n);
-    int k = 0;
-    for (size_t off = 0; off < n; off += ch, ++k) {
-        const size_t len = n - off < ch ? n - off : ch;
-        if (!c->ev[k]) check(hipEventCreateWithFlags(&c->ev[k], hipEventDisableTiming), "hipEventCreate");
-        check(hipMemcpyAsync(c->h_out + off, d_src + off, len, hipMemcpyDeviceToHost, c->s), "D2H");
-        check(hipEventRecord(c->ev[k], c->s), "hipEventRecord");
-    }
-    k = 0;
-    for (size_t off = 0; off < n; off += ch, ++k) {
-        const size_t len = n - off < ch ? n - off : ch;
-        check(hipEventSynchronize(c->ev[k]), "hipEventSynchronize");
-        memcpy(q + off, c->h_out + off, len);
-    }
+    check(hipMemcpyAsync(c->h_out, d_src, n, hipMemcpyDeviceToHost, c->s), "D2H");
+    check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
+    memcpy(q, c->h_out, n);
 }
 
 // Small calls (the route's small bodies, rle_route.h).  Zero-copy (default): the caller's bytes,
@@ -957,147 +898,6 @@ void presize(Ctx* c) {
     } catch (const std::bad_alloc&) {
     }
 }
-
-#if RLE_VARIANTS
-// ---------------------------------------------------------------- coalescing of concurrent small calls
-// The server's worker threads (src/server.c:520-524) call the codec concurrently -- reads of
-// different files decode outside the store lock (src/filesystemApi.c:570 -> 597) -- and a 4 KiB
-// call is bound by its fixed cost (one launch, one sync: ~18 us), not by the GPU.  So concurrent
-// zero-copy calls on one device join one batched launch (flat combining): each caller puts its
-// bytes in its own mapped buffer and a request on the device's queue; whichever caller finds no
-// batch in flight becomes the combiner, takes every queued request, issues one encode and/or one
-// decode launch over all of them on its stream (the kernels read and write the callers' mapped
-// buffers; offsets are relative to the lowest buffer address), syncs once and marks each request
-// done.  Requests that arrive meanwhile wait for the next combiner.  A caller alone pays two mutex
-// operations more than before.  Outputs are the same bytes: each buffer is independent
-// (src/rleCompression.c:9-62).
-// Off by default (RLE_MI355X_COALESCE=1 turns it on): measured with tools/callrate (4 KiB round
-// trips, r3d), one stream per thread already overlaps the calls on the GPU's hardware queues --
-// 55.8 K calls/s on 1 thread, 98.7 K on 2, 250.6 K on 8, 291.7 K on 16 -- while combining serialises
-// them behind the batch in flight: 52.9 K, 145.2 K and 248.6 K calls/s on 2, 8 and 16 threads.
-constexpr uint32_t kMaxCoalesce = 256;   // requests per combined launch
-struct Req {
-    const uint8_t* d_buf;   // the caller's mapped buffer (device address): input at kZcIn, output at kZcOut
-    uint64_t in_len;        // encode: U; decode: C
-    uint64_t out_len;       // decode: U
-    uint64_t cap;           // decode: U + E
-    bool dec;
-    uint64_t result;        // encode: C; decode: status
-    std::atomic<int> done{0};
-};
-struct Combiner {
-    std::mutex m;
-    std::vector<Req*> q;
-    std::atomic<bool> busy{false};
-};
-constexpr int kMaxDev = 64;
-Combiner g_comb[kMaxDev];
-
-// Launch words of one combined launch in the combiner's mapped buffer: per kind 5 u64 arrays (in_off,
-// in_len, out_off, out_len, out_cap) and the u32 statuses.
-constexpr size_t kCwBytes = 2 * (5 + 1) * 8 * kMaxCoalesce;
-uint64_t* cw(Ctx* c, uint64_t** dev) {
-    mapped(c->h_cw, c->d_cw, kCwBytes);
-    *dev = reinterpret_cast<uint64_t*>(c->d_cw);
-    return reinterpret_cast<uint64_t*>(c->h_cw);
-}
-
-// One combined launch per kind over reqs[0, m), on c's stream, one sync.
-void run_batch(Ctx* c, Req* const* reqs, uint32_t m) {
-    uint64_t* dw = nullptr;
-    uint64_t* hw = cw(c, &dw);
-    const uint8_t* base = reqs[0]->d_buf;
-    for (uint32_t i = 1; i < m; ++i) base = std::min(base, reqs[i]->d_buf);
-    for (int dec = 0; dec < 2; ++dec) {
-        uint64_t* h = hw + (size_t)dec * (5 + 1) * kMaxCoalesce;   // 5 u64 arrays + room for the statuses
-        uint64_t* d = dw + (size_t)dec * (5 + 1) * kMaxCoalesce;
-        uint32_t k = 0;
-        uint64_t max_in = 0, max_out = 0;
-        for (uint32_t i = 0; i < m; ++i) {
-            const Req* r = reqs[i];
-            if (r->dec != (dec != 0)) continue;
-            const uint64_t off = (uint64_t)(r->d_buf - base);
-            h[k] = off + kZcIn;
-            h[kMaxCoalesce + k] = r->in_len;
-            h[2 * kMaxCoalesce + k] = off + kZcOut;
-            h[3 * kMaxCoalesce + k] = r->out_len;
-            h[4 * kMaxCoalesce + k] = r->cap;
-            max_in = std::max(max_in, r->in_len);
-            max_out = std::max(max_out, r->out_len);
-            ++k;
-        }
-        if (!k) continue;
-        uint32_t* dst = reinterpret_cast<uint32_t*>(d + 5 * kMaxCoalesce);
-        uint8_t* obase = const_cast<uint8_t*>(base);
-        const int rc = dec ? rle_decode_batch_device_sized(base, d, d + kMaxCoalesce, obase, d + 2 * kMaxCoalesce,
-                                                           d + 3 * kMaxCoalesce, d + 4 * kMaxCoalesce, dst, k, max_in,
-                                                           max_out, c->s)
-                           : rle_encode_batch_device_sized(base, d, d + kMaxCoalesce, obase, d + 2 * kMaxCoalesce,
-                                                           d + 3 * kMaxCoalesce, dst, k, max_in, c->s);
-        if (rc != RLE_OK) die(dec ? "decode launch" : "encode launch", hipGetLastError());
-    }
-    check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
-    uint32_t ke = 0, kd = 0;
-    for (uint32_t i = 0; i < m; ++i) {
-        Req* r = reqs[i];
-        if (r->dec) {
-            const uint32_t* st = reinterpret_cast<const uint32_t*>(hw + (5 + 1) * kMaxCoalesce + 5 * kMaxCoalesce);
-            r->result = st[kd++];
-        } else {
-            r->result = hw[3 * kMaxCoalesce + ke++];
-        }
-        r->done.store(1, std::memory_order_release);
-    }
-    g_stats.launches_coalesced++;
-    g_stats.calls_coalesced += m;
-}
-
-// Queue r on the device's combiner and return once it is done (this thread may run the batch).
-void submit(Ctx* c, Req* r) {
-    Combiner& cb = g_comb[c->dev % kMaxDev];
-    {
-        std::lock_guard<std::mutex> g(cb.m);
-        cb.q.push_back(r);
-    }
-    Req* batch[kMaxCoalesce];
-    for (unsigned spin = 0; !r->done.load(std::memory_order_acquire); ++spin) {
-        if (!cb.busy.load(std::memory_order_relaxed) && !cb.busy.exchange(true, std::memory_order_acquire)) {
-            uint32_t m = 0;
-            {
-                std::lock_guard<std::mutex> g(cb.m);
-                m = (uint32_t)std::min<size_t>(cb.q.size(), kMaxCoalesce);
-                std::copy(cb.q.begin(), cb.q.begin() + m, batch);
-                cb.q.erase(cb.q.begin(), cb.q.begin() + m);
-            }
-            if (m) {
-                try {
-                    run_batch(c, batch, m);
-                } catch (...) {   // allocation failure of the launch words: every waiter must still finish
-                    for (uint32_t i = 0; i < m; ++i) {
-                        batch[i]->result = ~0ull;
-                        batch[i]->done.store(1, std::memory_order_release);
-                    }
-                }
-            }
-            cb.busy.store(false, std::memory_order_release);
-        } else if (spin > 64) {
-            sched_yield();
-        }
-    }
-    if (r->result == ~0ull) throw std::bad_alloc();
-}
-
-// One call on c's mapped buffer through the combiner: returns C (encode) or the status (decode).
-uint64_t coalesced(Ctx* c, bool dec, uint64_t in_len, uint64_t out_len, uint64_t cap) {
-    Req r;
-    r.d_buf = c->d_zc; r.in_len = in_len; r.out_len = out_len; r.cap = cap; r.dec = dec; r.result = 0;
-    submit(c, &r);
-    return r.result;
-}
-#else
-// (the product library never sets Settings::coalesce, so no route is Body::MappedCoalesce)
-inline uint64_t coalesced(Ctx*, bool, uint64_t, uint64_t, uint64_t) { die("coalescing: not built in", hipErrorUnknown); }
-#endif  // RLE_VARIANTS
 
 // Launch flags and completion wait of a zero-copy call (g_poll): the status word in the mapped
 // buffer is preset to kPending and polled, spinning for kSpinNs, then yielding the core between
@@ -1139,135 +939,6 @@ uint32_t zc_wait(Ctx* c, const uint64_t* status_word) {
     if (g_poll && v == kPending) die("status never stored", hipErrorUnknown);
     return v;
 }
-
-// ---------------------------------------------------------------- resident small-call service
-// Measured slower than the per-call launches at 8 threads and behind the server (DESIGN.md §6,
-// profiles/r4r_callrate.txt, r4r_e2e_compare.json), so since round 5 it is built only into the
-// RLE_VARIANTS test library (RLE_MI355X_SERVICE=1 there); the product library carries stubs.
-constexpr uint32_t kSvcStopped = 0xFFFFFFFFu;   // svc_call: not served (below)
-#if RLE_VARIANTS
-// (rle_service.h): one resident workgroup per thread context, on the context's own service stream,
-// its mailbox in the context's mapped buffer.  g_svc_m guards the registry of contexts with a
-// service, which process exit stops (svc_stop).
-extern "C" int rle_service_launch(void* d_mail, const void* d_src, void* d_dst, uint32_t gen, uint32_t done,
-                                  void* stream);
-constexpr size_t kZcMail = rle::kZcWords + 2048;   // the mailbox's offset in the mapped buffer (64-byte aligned)
-constexpr int kSvcMax = 256;                  // contexts with a service at once (the rest launch per call)
-pthread_mutex_t g_svc_m = PTHREAD_MUTEX_INITIALIZER;
-Ctx* g_svc_ctx[kSvcMax];
-int g_svc_n = 0;
-
-// Whether context c serves its small calls through its resident service (set up on first use).
-bool svc_on(Ctx* c) {
-    if (c->svc != -2) return c->svc > 0;
-    c->svc = -1;
-    if (!g_set.service) return false;
-    zc(c);
-    pthread_mutex_lock(&g_svc_m);
-    const bool room = g_svc_n < kSvcMax;
-    if (room) g_svc_ctx[g_svc_n++] = c;
-    pthread_mutex_unlock(&g_svc_m);
-    if (!room) return false;
-    // The service stream at the greatest priority: the runtime serves each priority from its own
-    // hardware queues, so the resident workgroup never shares a queue with the contexts' normal
-    // streams, whose dependent launches (a call's second kernel waits for its first) would otherwise
-    // wait behind it until it idles out (tools/probes/queue_probe.hip).
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (hipStreamCreateWithPriority(&c->svc_s, hipStreamNonBlocking, prio_hi) != hipSuccess) {
-        (void)hipGetLastError();
-        c->svc_s = nullptr;
-        return false;   // (stays registered: svc_stop skips a context without a stream)
-    }
-    c->svc_h = reinterpret_cast<rle::SvcMail*>(c->h_zc + kZcMail);
-    c->svc_d = reinterpret_cast<rle::SvcMail*>(c->d_zc + kZcMail);
-    memset(c->svc_h, 0, sizeof(rle::SvcMail));
-    c->svc = 1;
-    return true;
-}
-// A running service for c's request just posted: launch one when there is none or the last has ended
-// (wait for that launch to complete first).
-std::atomic<bool> g_svc_stopped{false};   // svc_stop ran: no service is launched again
-bool svc_ensure(Ctx* c) {
-    if (c->svc_gen && __atomic_load_n(&c->svc_h->a.gone, __ATOMIC_ACQUIRE) != c->svc_gen) return true;
-    if (g_svc_stopped.load(std::memory_order_acquire)) return false;
-    if (c->svc_gen) check(hipStreamSynchronize(c->svc_s), "hipStreamSynchronize(service)");
-    const uint32_t done = __atomic_load_n(&c->svc_h->a.ack, __ATOMIC_ACQUIRE);
-    launched(rle_service_launch(c->svc_d, c->d_zc + kZcIn, c->d_zc + kZcOut, c->svc_gen + 1u, done, c->svc_s),
-             "service launch");
-    ++c->svc_gen;
-    return true;
-}
-// End c's service and wait for it (thread exit, process exit).
-void svc_end(Ctx* c) {
-    if (c->svc <= 0 || !c->svc_s) return;
-    if (c->svc_gen) {
-        __atomic_store_n(&c->svc_h->r.stop, 1u, __ATOMIC_RELEASE);
-        (void)hipStreamSynchronize(c->svc_s);
-    }
-    (void)hipStreamDestroy(c->svc_s);
-    c->svc_s = nullptr;
-    c->svc = -1;
-}
-void svc_unregister(Ctx* c) {
-    pthread_mutex_lock(&g_svc_m);
-    for (int i = 0; i < g_svc_n; ++i)
-        if (g_svc_ctx[i] == c) {
-            g_svc_ctx[i] = g_svc_ctx[--g_svc_n];
-            break;
-        }
-    pthread_mutex_unlock(&g_svc_m);
-}
-// At exit (on_exit_handler, before the runtime's teardown): every service ends.
-void svc_stop() {
-    g_svc_stopped.store(true, std::memory_order_release);
-    pthread_mutex_lock(&g_svc_m);
-    for (int i = 0; i < g_svc_n; ++i)
-        if (g_svc_ctx[i]->svc > 0 && g_svc_ctx[i]->svc_gen) __atomic_store_n(&g_svc_ctx[i]->svc_h->r.stop, 1u, __ATOMIC_RELEASE);
-    for (int i = 0; i < g_svc_n; ++i)
-        if (g_svc_ctx[i]->svc > 0 && g_svc_ctx[i]->svc_gen) (void)hipStreamSynchronize(g_svc_ctx[i]->svc_s);
-    pthread_mutex_unlock(&g_svc_m);
-}
-// One request on c's mapped buffer: returns the status, *res_len the encoded size.  The line is
-// written with the sequence number last (tail, then req); the wait polls ack, checking every 256
-// polls that the service has not ended before taking the request.  Once process exit has stopped
-// the services (svc_stop) a request that finds its service gone is not served: kSvcStopped, and the
-// caller takes the launch path (a relaunch would exit at once on the stop word).
-uint32_t svc_call(Ctx* c, uint32_t op, uint64_t in_len, uint64_t out_len, uint64_t cap, uint64_t* res_len) {
-    rle::SvcReq* r = &c->svc_h->r;
-    r->op = op;
-    r->in_len = (uint32_t)in_len;
-    r->out_len = (uint32_t)out_len;
-    r->cap = (uint32_t)cap;
-    r->flags = 1u;   // write-through stores (the output leaves the L2 at once)
-    const uint32_t seq = ++c->svc_seq;
-    __atomic_store_n(&r->tail, seq, __ATOMIC_RELEASE);
-    __atomic_store_n(&r->req, seq, __ATOMIC_RELEASE);
-    if (!svc_ensure(c)) return kSvcStopped;
-    const uint64_t t0 = now_ns();
-    bool yield = false;
-    for (uint32_t i = 1;; ++i) {
-        if (__atomic_load_n(&c->svc_h->a.ack, __ATOMIC_ACQUIRE) == seq) break;
-        if ((i & 255u) == 0u) {
-            if (!svc_ensure(c) && __atomic_load_n(&c->svc_h->a.ack, __ATOMIC_ACQUIRE) != seq) return kSvcStopped;
-            const uint64_t t = now_ns() - t0;
-            if (t > 10000000000ull) die("service request (10 s)", hipErrorUnknown);
-            yield = t > g_spin_ns;
-        }
-        if (yield) sched_yield();
-        else __builtin_ia32_pause();
-    }
-    if (res_len) *res_len = __atomic_load_n(&c->svc_h->a.res_len, __ATOMIC_ACQUIRE);
-    return __atomic_load_n(&c->svc_h->a.status, __ATOMIC_ACQUIRE);
-}
-
-#else
-inline bool svc_on(Ctx*) { return false; }
-inline uint32_t svc_call(Ctx*, uint32_t, uint64_t, uint64_t, uint64_t, uint64_t*) { return kSvcStopped; }
-void svc_end(Ctx*) {}
-void svc_unregister(Ctx*) {}
-void svc_stop() {}
-#endif  // RLE_VARIANTS (resident service)
 
 }  // namespace
 
@@ -1325,11 +996,7 @@ char* compress_small_zc(Ctx* c, Body body, const char* data, size_t U, size_t* c
     const ZcWords w(c);
     uint64_t C = 0;
     uint32_t st = RLE_STATUS_OK;
-    switch (body) {
-    case Body::MappedCoalesce:
-        C = coalesced(c, false, U, 0, 0);
-        break;
-    case Body::MappedSeg:
+    if (body == Body::MappedSeg) {
         w.encode(kZcIn, U, 0, 0);
         grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, U));
         launched(rle_encode_batch_device_seg(c->d_zc, w.d + 0, w.d + 1, c->d_zc + kZcOut, w.d + 2, w.d + 3,
@@ -1338,11 +1005,7 @@ char* compress_small_zc(Ctx* c, Body body, const char* data, size_t U, size_t* c
         check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
         st = w.status(ZcWords::kEncStatus);
         C = w.encoded_len();
-        break;
-    case Body::MappedService:
-        if (svc_on(c) && (st = svc_call(c, rle::kSvcEncode, U, 0, 0, &C)) != kSvcStopped) break;
-        [[fallthrough]];   // (no service on this thread, or stopped at exit: a launch)
-    default:
+    } else {
         zc_encode_one(c, w, kZcIn, U, kZcOut);
         st = zc_wait(c, w.h + ZcWords::kEncStatus);
         C = w.encoded_len();
@@ -1358,21 +1021,13 @@ void decompress_small_zc(Ctx* c, Body body, const char* data, size_t C, size_t U
     memcpy(h + kZcIn, data, C);
     const ZcWords w(c);
     uint32_t st;
-    switch (body) {
-    case Body::MappedCoalesce:
-        st = (uint32_t)coalesced(c, true, C, U, total);
-        break;
-    case Body::MappedSeg:
+    if (body == Body::MappedSeg) {
         w.decode(kZcIn, C, 0, U, total, 0);
         grow_dev(c->d_ws, c->d_ws_cap, rle_seg_workspace_bytes(1, C));
         launch_decode(c, true, c->d_zc, c->d_zc + kZcOut, w.d, C, U);
         check(hipStreamSynchronize(c->s), "hipStreamSynchronize");
         st = w.status(ZcWords::kDecStatus);
-        break;
-    case Body::MappedService:
-        if (svc_on(c) && (st = svc_call(c, rle::kSvcDecode, C, U, total, nullptr)) != kSvcStopped) break;
-        [[fallthrough]];
-    default:
+    } else {
         zc_decode_one(c, w, kZcIn, C, kZcOut, U, total);
         st = zc_wait(c, w.h + ZcWords::kDecStatus);
     }
@@ -1440,7 +1095,7 @@ void warm_small(Ctx* c) {
 // staging), which set up the copy engines and the runtime's own staging buffers on first use.
 void warm(Ctx* c) {
     const LargeCall lc(c->s);   // (its own buffers; a registration elsewhere only stages its copies)
-    constexpr size_t kBig = kPipeMinBytes + (64u << 10), kMed = 64u << 10, kSmall = 4096;
+    constexpr size_t kBig = kDirectMinBytes + (64u << 10), kMed = 64u << 10, kSmall = 4096;
     std::vector<uint8_t> buf(kBig), back(kBig);
     for (size_t i = 0; i < kBig; ++i) buf[i] = (uint8_t)(((i * 2654435761u) >> 13) & 3u);   // short runs
     const char* b = reinterpret_cast<const char*>(buf.data());
@@ -1862,7 +1517,7 @@ struct NTotals : Stats::Call {   // of one RLEdecompressN call: summed over its 
 };
 
 // RLEdecompressN of one file too large for the bounded staging: straight from / to caller memory
-// whatever RLE_MI355X_STAGING says (the pinned and pipe modes would grow this thread's staging to
+// whatever RLE_MI355X_STAGING says (the pinned mode would grow this thread's staging to
 // the file's size, which g_stage_cap exists to prevent).
 // Bytes whose pages meet another call's registration (live_pages) go through the staging in
 // chunks of at most g_stage_cap instead, a synchronize per chunk.
@@ -2100,8 +1755,7 @@ extern "C" int rle_mi355x_dropin_stats(rle_dropin_stats_t* out, int reset) {
     out->ns_stage_in = g_stats.ns_stage_in.load();
     out->ns_device = g_stats.ns_device.load();
     out->ns_stage_out = g_stats.ns_stage_out.load();
-    out->calls_coalesced = g_stats.calls_coalesced.load();
-    out->launches_coalesced = g_stats.launches_coalesced.load();
+    out->calls_coalesced = out->launches_coalesced = 0;   // (call coalescing is retired; the layout stays)
     out->calls_registered = g_stats.calls_registered.load();
     out->calls_reg_fallback = g_stats.calls_reg_fallback.load();
     out->calls_append_spliced = g_stats.calls_append_spliced.load();
@@ -2109,8 +1763,6 @@ extern "C" int rle_mi355x_dropin_stats(rle_dropin_stats_t* out, int reset) {
         g_stats.calls_compress = 0; g_stats.calls_decompress = 0; g_stats.calls_append = 0; g_stats.bytes_in = 0; g_stats.bytes_out = 0;
         g_stats.bytes_h2d = 0; g_stats.bytes_d2h = 0; g_stats.ns_stage_in = 0; g_stats.ns_device = 0;
         g_stats.ns_stage_out = 0;
-        g_stats.calls_coalesced = 0;
-        g_stats.launches_coalesced = 0;
         g_stats.calls_registered = 0;
         g_stats.calls_reg_fallback = 0;
         g_stats.calls_append_spliced = 0;

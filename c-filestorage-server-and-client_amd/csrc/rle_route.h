@@ -3,7 +3,7 @@
 // compiler builds it, and tests/test_route.py pins the decisions on a machine without a GPU.
 // What depends on device or process state is not part of a route and stays with the calls: the
 // cooperative kernels' own admission (rle_*_coop_one returning 0), whether a call that wants
-// registration gets it (reg_likely, LargeCall::registered), live_pages, a thread's service (svc_on).
+// registration gets it (reg_likely, LargeCall::registered), live_pages.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -58,20 +58,15 @@ struct Settings {
     // From reg_min bytes a call wants its buffers registered for its duration (rle_dropin.cpp,
     // LargeCall; RLE_MI355X_REG_MIN; 0 = never; past the zero-copy calls: r6m / r6o).
     size_t reg_min = kZcMaxIn + 1;
-    int fake_devs = 0;       // test build: contexts without HIP objects (RLE_MI355X_FAKE_DEVICES); none registers
-    // RLE_VARIANTS builds only (measured slower):
-    bool coalesce = false;   // concurrent zero-copy calls join one launch (submit); RLE_MI355X_COALESCE=1: on
-    bool service = false;    // small calls through the resident service (rle_service.h); RLE_MI355X_SERVICE=1
+    int fake_devs = 0;   // test build: contexts without HIP objects (RLE_MI355X_FAKE_DEVICES); none registers
 };
 
 // The body that runs an RLEcompress / RLEdecompress.
 enum class Body : uint8_t {
-    MappedOne,        // mapped buffer, one launch: the cooperative workgroup, else one wave (polled)
-    MappedSeg,        // mapped buffer, the segmented kernels (one stream sync)
-    MappedCoalesce,   // mapped buffer, joined with other threads' calls in one launch (variants)
-    MappedService,    // mapped buffer, the resident service if this thread's is alive, else MappedOne (variants)
-    Staged,           // one H2D, one one-wave launch, one D2H (RLE_MI355X_SMALL=copy)
-    Large,            // device buffers: the caller's bytes by DMA or the runtime's pageable copies
+    MappedOne,   // mapped buffer, one launch: the cooperative workgroup, else one wave (polled)
+    MappedSeg,   // mapped buffer, the segmented kernels (one stream sync)
+    Staged,      // one H2D, one one-wave launch, one D2H (RLE_MI355X_SMALL=copy)
+    Large,       // device buffers: the caller's bytes by DMA or the runtime's pageable copies
 };
 // A buffer in device memory (queue_encode / queue_decode, the registered calls): the segmented
 // kernels or one wave, and whether an encode's worst-case output travels with its size.
@@ -92,11 +87,7 @@ constexpr bool coop_decodes(size_t C, size_t U, const Settings& s) {
     return s.zc_coop && C <= kCoopDecMaxIn && U <= kCoopDecUmax;
 }
 constexpr Body small_body(bool seg, const Settings& s) {
-    return !s.zerocopy ? Body::Staged
-           : s.coalesce ? Body::MappedCoalesce
-           : seg        ? Body::MappedSeg
-           : s.service  ? Body::MappedService
-                        : Body::MappedOne;
+    return !s.zerocopy ? Body::Staged : seg ? Body::MappedSeg : Body::MappedOne;
 }
 
 // RLEcompress of U > 0 bytes.  (Registered encodes are segmented; the cooperative kernel's stay zero-copy.)

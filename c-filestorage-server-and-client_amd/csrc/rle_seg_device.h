@@ -101,20 +101,11 @@ __device__ __forceinline__ bool owned_any(bool x) {
     return (__builtin_amdgcn_ballot_w64(x) & ((1ull << kOwnLanes) - 1ull)) != 0ull;
 }
 
-// A segment's tile walk: through the double-buffered LDS-DMA slots (walk_tiles), or (kRes) over a
-// segment already resident in LDS (res_load): tile t at mem + 1008 t, nothing to load or wait for.
-template <bool kRes, class Step>
-__device__ __forceinline__ bool walk_seg(u32x4 rs, u32 start, u32 ntiles, u32 lane, const uint8_t* mem, Step step) {
-    if (kRes) {
-#pragma clang loop unroll(disable)
-        for (u32 t = 0; t < ntiles; ++t)
-            if (step(t, mem + t * kTileStep, Refill{rs, 0u, 0u, false, false}) == ~0u) {
-                vm_drain();
-                return true;
-            }
-        return false;
-    }
-    return walk_tiles(rs, start, ntiles, lane, mem, step);
+// A segment's tile walk: walk_tiles (rle_device.h) through the wave's two LDS-DMA slots.  (Its own
+// inlined function: the segment kernels' instruction order depends on it, checked in the listings.)
+template <class Step>
+__device__ __forceinline__ bool walk_seg(u32x4 rs, u32 start, u32 ntiles, u32 lane, const uint8_t* slots, Step step) {
+    return walk_tiles(rs, start, ntiles, lane, slots, step);
 }
 
 // compressed bytes of the tokens starting in a segment's entering run piece (length L0) when the
@@ -141,7 +132,6 @@ __device__ __forceinline__ u32 seg_prev_top(const uint8_t* src, u32 p0, SegEntry
 
 // One segment's encode summary (L0, lb + 1 or 0, rest, cont; see the top of rle_segmented.hip): a
 // walk over its tiles, analysis only.  U > 0, src 16-byte aligned.
-template <bool kRes = false>
 __device__ __forceinline__ uint4 enc_seg_summarize(const uint8_t* src, u32 U, u32 p0, u32 p1, u32 lane,
                                                    const uint8_t* slots, SegEntry en = SegEntry{false, 0u}) {
     const u32x4 rsi = make_rsrc(src, (U + 15u) & ~15u);
@@ -149,7 +139,7 @@ __device__ __forceinline__ uint4 enc_seg_summarize(const uint8_t* src, u32 U, u3
     u32 rs = p0, fb = kNone, lb = kNone, rest = 0;
     u32 restl = 0u, lbl = 0u;   // the lane's token bytes and its last boundary + 1 (0: none), summed once per segment
     const EncK kc = enc_k();
-    walk_seg<kRes>(rsi, p0, ntiles_for(p1 - p0), lane, slots, [&](u32 t, const uint8_t* cs, const Refill& nx) {
+    walk_seg(rsi, p0, ntiles_for(p1 - p0), lane, slots, [&](u32 t, const uint8_t* cs, const Refill& nx) {
         const u32x4 cur = *reinterpret_cast<const u32x4*>(cs + 16u * lane);
         nx();
         const u32 pos = p0 + t * kTileStep;
@@ -207,7 +197,7 @@ __device__ __forceinline__ uint4 enc_seg_summarize(const uint8_t* src, u32 U, u3
 // The carried state of an encode scan over a buffer's segments: max (lb + 1) so far, and the output
 // offset.  One window of up to 64 consecutive segments (lane i: segment base + i, summary sm, first
 // position p0), entered with c: each lane's entering run start and output offset; c advances past
-// the window.  Shared by the per-buffer scan and the fused kernel's look-back.
+// the window.
 struct EncCarry {
     u32 lb1, off;
 };
@@ -229,7 +219,6 @@ __device__ __forceinline__ uint2 enc_seg_window(uint4 sm, bool valid, u32 p0, En
 // One segment's output: the tile walk from its entering run start rs and output offset off.
 // obound: the bytes of dst the stores may reach (0: the encode's U + U / 2; the append passes its
 // slot, whose output starts behind the stored stream).
-template <bool kRes = false>
 __device__ __forceinline__ void enc_seg_write(const uint8_t* src, uint8_t* dst, u32 U, u32 p0, u32 p1, u32 rs,
                                               u32 off, u32 lane, const uint8_t* slots, uint8_t* stage,
                                               const u32* elut, SegEntry en = SegEntry{false, 0u}, u32 obound = 0u) {
@@ -237,7 +226,7 @@ __device__ __forceinline__ void enc_seg_write(const uint8_t* src, uint8_t* dst, 
     const u32x4 rso = make_rsrc(dst, obound ? obound : U + U / 2u);
     EncState st{off, off & ~15u, seg_prev_top(src, p0, en), rs, off & 15u, false, {}};
     const EncK kc = enc_k();
-    walk_seg<kRes>(rsi, p0, ntiles_for(p1 - p0), lane, slots, [&](u32 t, const uint8_t* cs, const Refill& nx) {
+    walk_seg(rsi, p0, ntiles_for(p1 - p0), lane, slots, [&](u32 t, const uint8_t* cs, const Refill& nx) {
         // the fast tile paths (round 3; until then only the one-wave kernels took them): past the
         // segment's shared first chunk and before its last tile, as in a one-wave walk
         return enc_tile<false, true>(cs, nx, p0 + t * kTileStep, U, p1, lane, stage, dst, rso, st, kc, elut);
@@ -383,9 +372,6 @@ struct SegShape {
     uint4* summ;
     uint2* plan;
     uint32_t* bflag;
-    uint32_t* sflag;    // single-pass variants: per-segment publication flag
-    uint4* incl;        // single-pass variants: per-segment inclusive state
-    uint32_t* ticket;   // single-pass variants: segment ticket counter
     void* extra;
     size_t bytes;
 };
@@ -395,9 +381,7 @@ struct SegShape {
 // queries call it without a workspace and read sh->bytes.
 int seg_prologue(void* d_workspace, size_t workspace_bytes, uint32_t n, uint64_t total, size_t extra, SegShape* sh);
 // The plan and map launches over `len` into seg_first and seg_buf of the shape; none for one buffer.
-// The single-pass variants have the plan clear their flags, ticket and per-buffer words as well.
-void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hipStream_t s,
-                         uint32_t* sflag = nullptr, uint32_t* ticket = nullptr, uint32_t* bclear = nullptr);
+void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hipStream_t s);
 // The decode's summary launch over the streams `in + off[i]` of `len[i]` bytes into the shape's
 // summaries (dec_seg_summary_kernel: per segment and entry phase 0..2 the decoded bytes in .x .y .z,
 // the exit phases in .w bits 0..5 and the phases whose parse stops in bits 8..10).  The segmented

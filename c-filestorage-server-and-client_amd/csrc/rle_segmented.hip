@@ -27,17 +27,6 @@
 
 namespace rle {
 
-// The decode summary's phase-free count of literal tiles (dec_count_phasefree, round 6): off.  r6be /
-// r6bf, rocprof medians of the summary kernel (1024 x 1 MiB random / runs50 / configs[2] mixed):
-// tried on every tile 236.1 / 364.9 / 80.3 µs, with the back-off below 256.7 / 291.1 / 70.7, off
-// 268.2-269.7 / 269.4-276.5 / 63.6-66.0.  The random gain does not pay for the run-heavy loss.
-#ifndef RLE_SEG_PHASEFREE
-#define RLE_SEG_PHASEFREE 0
-#endif
-#ifndef RLE_SEG_PF_WAIT
-#define RLE_SEG_PF_WAIT 8
-#endif
-
 // decode write pass staging (chunks per wave, rle_device.h kDecChunks): the launcher takes the
 // one-pass 192-chunk kernel when every segment is resident at once, else the 96-chunk one (7 instead
 // of 4 workgroups per CU; r3s A/B: 1 MiB random -9 %, mixed batch -27 %, one 64 MiB file +7 % with 96)
@@ -49,18 +38,9 @@ constexpr u32 kSegDecChunksOne = RLE_DEC_CHUNKS, kSegDecChunksMany = 96;
 
 // seg_first[i] = segments of buffers < i; seg_first[n] = total.  One workgroup.
 __global__ __launch_bounds__(1024) void seg_plan_kernel(const uint64_t* __restrict__ len, u32 n, u32 sb,
-                                                        u32* __restrict__ seg_first, u32* __restrict__ sflag,
-                                                        u32 maxseg, u32* __restrict__ ticket,
-                                                        u32* __restrict__ bclear) {
+                                                        u32* __restrict__ seg_first) {
     __shared__ u32 part[1024];
     const u32 t = threadIdx.x;
-    // (fused kernels) every segment's publication flag cleared, the ticket counter at 0, and (the
-    // single-pass decode) every buffer's flags
-    if (sflag)
-        for (u32 i = t; i < maxseg; i += 1024u) sflag[i] = 0u;
-    if (bclear)
-        for (u32 i = t; i < n; i += 1024u) bclear[i] = 0u;
-    if (ticket && t == 0u) *ticket = 0u;
     const u32 per = (n + 1023u) / 1024u;
     const u32 b0 = t * per < n ? t * per : n;
     const u32 b1 = b0 + per < n ? b0 + per : n;
@@ -178,266 +158,6 @@ __global__ __launch_bounds__(kSegBlock) void enc_seg_write_kernel(const uint8_t*
                        stage_all, elut, [=](u32 b) { return enc_view(in, in_off, in_len, out, out_off, b); });
 }
 
-// ================================================================ measured-slower variants
-// (RLE_VARIANTS builds only: the test library build/librle_mi355x_testhooks.so and `make variant`;
-// never the product librle_mi355x.so.  VERDICT r3 item 8.)  The fused single-pass encode and the
-// resident single-pass kernels are bit-exact and tested, but slower than the five-launch default
-// ("Round 3: segmented path"), so the product does not carry them.
-#if RLE_VARIANTS
-// ---------------------------------------------------------------- fused single-pass encode
-// One launch after the plan (SURVEY.md §5's single-pass form, with a decoupled look-back carry):
-// waves take segments in ticket order (a global counter), summarise their segment, publish the
-// summary (flag 1), derive their entering state from the published summaries and inclusive states
-// of the segments before them in the same buffer, publish their own inclusive state (flag 2), and
-// write their output at once: the segment's bytes are read a second time right after the first,
-// while they are still in the caches, and no separate scan launch waits for the whole batch.
-// Progress: a wave waits only on segments holding earlier tickets, whose waves are running and
-// never wait on later ones, so the earliest unfinished segment always advances.  The wait is
-// still bounded (kSpinMax polls); a wave that runs out publishes and marks its buffer
-// RLE_STATUS_INTERNAL instead of hanging (never seen; tests check the status is clean).
-constexpr u32 kSpinMax = 1u << 20;
-constexpr u32 kFlagAgg = 1u, kFlagIncl = 2u;
-// The hand-off follows MI355X_MICROARCH.md's write-through form (per-XCD L2s are not coherent, and
-// an agent release fence would write back the XCD's whole dirty L2 after every segment): the
-// publishing lane stores every payload word and the flag write-through (relaxed agent-scope atomic
-// stores: `sc1`), with `s_waitcnt vmcnt(0)` between them; readers poll the flag and read the
-// payload with `sc1` loads (relaxed agent-scope atomic loads), never plain or scalar-cache loads.
-__device__ __forceinline__ u32 ld_relaxed(const u32* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_relaxed(u32* p, u32 v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint4 ld_relaxed4(const uint4* p) {
-    const u32* w = reinterpret_cast<const u32*>(p);
-    return make_uint4(ld_relaxed(w), ld_relaxed(w + 1), ld_relaxed(w + 2), ld_relaxed(w + 3));
-}
-// (one lane) payload, drain, flag
-__device__ __forceinline__ void publish(uint4* slot, uint4 v, u32* flag, u32 f) {
-    u32* w = reinterpret_cast<u32*>(slot);
-    st_relaxed(w, v.x);
-    st_relaxed(w + 1, v.y);
-    st_relaxed(w + 2, v.z);
-    st_relaxed(w + 3, v.w);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    st_relaxed(flag, f);
-}
-// The first segment this wave must combine forward: j + 1 for the nearest j in [s0, g) whose
-// inclusive state is published, or s0 (the buffer's start state) when none is; on return every
-// segment in [result, g) has published its summary.  Windows of 64 flags, nearest first.
-__device__ __forceinline__ u32 seg_lookback(u32 g, u32 s0, const u32* sflag, u32 lane, bool& late) {
-    u32 hi = g;
-    for (;;) {
-        const u32 lo = hi - s0 > kWave ? hi - kWave : s0;
-        const bool valid = lane < hi - lo;
-        const u32 j = valid ? hi - 1u - lane : hi - 1u;
-        u32 f = valid ? ld_relaxed(sflag + j) : kFlagAgg;
-        u32 polls = 0;
-        // wait only for the segments between this one and the nearest published inclusive state
-        // (or, when the window has none, for the whole window)
-        for (;;) {
-            const uint64_t m0 = __builtin_amdgcn_ballot_w64(f == 0u);
-            const uint64_t m2 = __builtin_amdgcn_ballot_w64(valid && f == kFlagIncl);
-            const uint64_t need = m2 ? (m2 & (0ull - m2)) - 1ull : ~0ull;
-            if (!(m0 & need) || ++polls > kSpinMax) {
-                if (m0 & need) late = true;
-                if (m2) return hi - (u32)__builtin_ctzll(m2);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-            if (f == 0u) f = ld_relaxed(sflag + j);
-        }
-        if (lo == s0) return s0;
-        hi = lo;
-    }
-}
-
-// the buffer holding global segment g: seg_first[b] <= g < seg_first[b + 1] (every buffer has a
-// segment, so seg_first is strictly increasing)
-__device__ __forceinline__ u32 seg_buffer(const u32* seg_first, u32 n, u32 g) {
-    u32 lo = 0, hi = n;
-    while (hi - lo > 1u) {
-        const u32 mid = (lo + hi) >> 1;
-        if (uniform(seg_first[mid]) <= g) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-// Resident segments (the resident single-pass kernels): a segment of at most kResTiles tiles
-// (segments are kResTiles - 1 tiles, a buffer's last one up to 2 bytes more) is loaded into the
-// wave's LDS region once, [p0, p0 + 1008 nt + 16) in 1 KiB LDS-DMAs (range-checked: zeros past the
-// buffer), and both its summary and its output walk read it there.
-#ifndef RLE_RES_TILES
-#define RLE_RES_TILES 8
-#endif
-constexpr u32 kResTiles = RLE_RES_TILES;
-constexpr u32 kResBytes = (kResTiles * kTileStep + 16u + 1023u) & ~1023u;
-constexpr u32 kResStride = kResBytes;
-#ifndef RLE_RES_DEC_CHUNKS   // the resident decode's staging (chunks per wave; its region takes LDS too)
-#define RLE_RES_DEC_CHUNKS 96
-#endif
-constexpr u32 kResDecChunks = RLE_RES_DEC_CHUNKS;
-__device__ __forceinline__ void res_load(u32x4 rs, u32 p0, u32 nt, u32 lane, const uint8_t* region) {
-    const u32 l0 = uniform(lds_addr(region));
-    const u32 nd = uniform((nt * kTileStep + 16u + 1023u) >> 10);
-    asm volatile("s_nop 4" ::: "memory");   // descriptor words may be fresh (walk_prime)
-    for (u32 k = 0; k < nd; ++k) dma_tile<true>(rs, p0 + 1024u * k + 16u * lane, l0 + 1024u * k);
-    vm_drain();
-}
-
-// What the encode kernel's arguments and LDS give a single-pass wave (mem: its two DMA slots, or its
-// resident region).
-struct EncSingle {
-    const uint8_t* in;
-    const uint64_t* in_off;
-    const uint64_t* in_len;
-    uint8_t* out;
-    const uint64_t* out_off;
-    uint64_t* out_len;
-    uint32_t* status;
-    const u32* seg_first;
-    u32 maxseg, sb;
-    uint4* summ;
-    uint4* incl;
-    u32* sflag;
-    u32 lane;
-    const uint8_t* mem;
-    uint8_t* stage;
-    const u32* elut;
-};
-// Segment g of buffer b in one pass, however the wave came by it (kRes: held in LDS): summarise and
-// publish the summary, derive the entering state from the segments before it, publish the inclusive
-// state, write.
-template <bool kRes>
-__device__ __forceinline__ void enc_seg_single(const EncSingle& a, u32 g, u32 b) {
-    const u32 lane = a.lane;
-    const u32 s0 = uniform(a.seg_first[b]), s1 = uniform(a.seg_first[b + 1]), nseg = s1 - s0;
-    const uint64_t U64 = a.in_len[b];
-    const uint8_t* src = a.in + a.in_off[b];
-    uint8_t* dst = a.out + a.out_off[b];
-    u32 bad = (((uintptr_t)src | (uintptr_t)dst) & 15u) ? RLE_STATUS_MISALIGNED : 0u;
-    if (U64 > kMaxBufferBytes || s1 > a.maxseg) bad |= RLE_STATUS_TOOLARGE;
-    if (bad || U64 == 0u) {   // the buffer's segments all skip (an empty buffer is one segment)
-        if (g == s0 && lane == 0) {
-            a.out_len[b] = 0;
-            if (a.status) a.status[b] = bad;
-        }
-        return;
-    }
-    const u32 U = (u32)U64;
-    u32 p0, p1;
-    seg_range(g - s0, nseg, U, a.sb, p0, p1);
-    if (kRes) res_load(make_rsrc(src, (U + 15u) & ~15u), p0, ntiles_for(p1 - p0), lane, a.mem);
-    const uint4 sm = enc_seg_summarize<kRes>(src, U, p0, p1, lane, a.mem);
-    if (lane == 0) publish(a.summ + g, sm, a.sflag + g, kFlagAgg);
-    // the state entering this segment: the nearest published inclusive state (or the buffer's
-    // start), then the summaries after it, 64 per window
-    bool late = false;
-    EncCarry c{0u, 0u};
-    u32 lateb = 0u;
-    if (g > s0) {
-        const u32 from = seg_lookback(g, s0, a.sflag, lane, late);
-        if (from > s0) {
-            const uint4 in4 = ld_relaxed4(a.incl + (from - 1u));
-            c = EncCarry{uniform(in4.x), uniform(in4.y)};
-            lateb = uniform(in4.z);
-        }
-        for (u32 base = from; base < g; base += kWave) {
-            const u32 j = base + lane;
-            const bool valid = j < g;
-            const uint4 smj = valid ? ld_relaxed4(a.summ + j) : make_uint4(0u, 0u, 0u, 0u);
-            enc_seg_window(smj, valid, (j - s0) * a.sb, c);
-        }
-    }
-    // this segment's own step (lane 0's window entry), published as its inclusive state
-    const uint2 mine = enc_seg_window(sm, lane == 0u, p0, c);
-    lateb |= late ? RLE_STATUS_INTERNAL : 0u;
-    if (lane == 0) {
-        publish(a.incl + g, make_uint4(c.lb1, c.off, lateb, 0u), a.sflag + g, kFlagIncl);
-        // the status words were cleared by the plan launch: a late segment ORs its bit in itself
-        // (a later segment may rebuild its state from raw summaries and not carry it), and the
-        // last segment ORs what it carries, so no bit is overwritten
-        if (late && a.status) atomicOr(a.status + b, RLE_STATUS_INTERNAL);
-        if (g + 1u == s1) {   // the buffer's last segment: C and the status
-            a.out_len[b] = c.off;
-            if (lateb && a.status) atomicOr(a.status + b, lateb);
-        }
-    }
-    enc_seg_write<kRes>(src, dst, U, p0, p1, uniform(mine.x), uniform(mine.y), lane, a.mem, a.stage, a.elut);
-}
-
-// The fused kernel takes segments in ticket order and finds a segment's buffer by binary search.
-__global__ __launch_bounds__(kSegBlock) void enc_seg_fused_kernel(const uint8_t* __restrict__ in,
-                                                                  const uint64_t* __restrict__ in_off,
-                                                                  const uint64_t* __restrict__ in_len,
-                                                                  uint8_t* __restrict__ out,
-                                                                  const uint64_t* __restrict__ out_off,
-                                                                  uint64_t* __restrict__ out_len,
-                                                                  uint32_t* __restrict__ status, u32 n,
-                                                                  const u32* __restrict__ seg_first, u32 maxseg, u32 sb,
-                                                                  uint4* __restrict__ summ, uint4* __restrict__ incl,
-                                                                  u32* __restrict__ sflag, u32* __restrict__ ticket) {
-    __shared__ __attribute__((aligned(16))) uint8_t slots_all[kSegWaves * 2 * kSlot];
-    __shared__ __attribute__((aligned(16))) uint8_t stage_all[kSegWaves * kEncStage];
-    __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];   // enc_tile_fast's selectors
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = uniform(threadIdx.x / kWave);
-    for (u32 k = threadIdx.x; k < kInsWaveWords; k += kSegBlock) elut[k] = kEncInsLut.s[k];
-    __syncthreads();
-    const EncSingle a{in,   in_off, in_len, out,  out_off, out_len, status, seg_first, maxseg, sb,
-                      summ, incl,   sflag,  lane, slots_all + wid * 2 * kSlot, stage_all + wid * kEncStage, elut};
-    u32 total = uniform(seg_first[n]);
-    total = total < maxseg ? total : maxseg;
-    for (;;) {
-        u32 g = 0;
-        if (lane == 0) g = atomicAdd(ticket, 1u);
-        g = uniform(g);
-        if (g >= total) break;
-        enc_seg_single<false>(a, g, seg_buffer(seg_first, n, g));
-    }
-}
-
-// ---------------------------------------------------------------- resident single-pass encode
-// SURVEY.md §5's single pass, with the segment held in LDS: a wave loads its segment's <= kResTiles
-// tiles into its LDS region once, summarises them there, publishes the summary, derives its entering
-// state with the decoupled look-back of the fused kernel above, publishes its inclusive state and
-// walks the same LDS tiles again to write.  HBM sees the input once.
-// One segment per wave, and since round 3 without the ticket counter: wave w of workgroup k takes
-// segment 4 k + w of a grid of one wave per segment.  (A wave holding several consecutive segments
-// published the later ones' summaries only after writing the earlier ones, so the waves behind it
-// in the same buffer waited for its whole batch; measured: the look-backs ran out of polls.)  A
-// workgroup is dispatched only after every lower-numbered workgroup of its XCD, so the
-// lowest-numbered waiting segment's predecessors are all running or done, and the look-back cannot
-// wait forever (and its polls are bounded regardless: a wave that runs out marks its buffer and
-// exits).
-__global__ __launch_bounds__(kSegBlock) void enc_seg_res_kernel(const uint8_t* __restrict__ in,
-                                                                const uint64_t* __restrict__ in_off,
-                                                                const uint64_t* __restrict__ in_len,
-                                                                uint8_t* __restrict__ out,
-                                                                const uint64_t* __restrict__ out_off,
-                                                                uint64_t* __restrict__ out_len,
-                                                                uint32_t* __restrict__ status, u32 n,
-                                                                const u32* __restrict__ seg_first,
-                                                                const u32* __restrict__ seg_buf, u32 maxseg, u32 sb,
-                                                                uint4* __restrict__ summ, uint4* __restrict__ incl,
-                                                                u32* __restrict__ sflag, u32* __restrict__ ticket) {
-    __shared__ __attribute__((aligned(16))) uint8_t region_all[kSegWaves * kResStride];
-    __shared__ __attribute__((aligned(16))) uint8_t stage_all[kSegWaves * kEncStage];
-    __shared__ __attribute__((aligned(16))) u32 elut[kInsWaveWords];   // enc_tile_fast's selectors
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = uniform(threadIdx.x / kWave);
-    for (u32 k = threadIdx.x; k < kInsWaveWords; k += kSegBlock) elut[k] = kEncInsLut.s[k];
-    __syncthreads();
-    const EncSingle a{in,   in_off, in_len, out,  out_off, out_len, status, seg_first, maxseg, sb,
-                      summ, incl,   sflag,  lane, region_all + wid * kResStride, stage_all + wid * kEncStage, elut};
-    u32 total = uniform(seg_first[n]);
-    total = total < maxseg ? total : maxseg;
-    (void)ticket;
-    const u32 g = blockIdx.x * kSegWaves + wid;   // one segment per wave
-    if (g < total) enc_seg_single<true>(a, g, uniform(seg_buf[g]));
-}
-#endif  // RLE_VARIANTS
-
 // ================================================================ DECODE
 // Decoded bytes of a non-tail tile entered at phase d when every pair token in it is "v v 2" (random
 // and text-like data): then each token's output is its own bytes with the count digit deleted, so
@@ -477,55 +197,6 @@ __device__ __forceinline__ u32 dec_count_literal(const DecPrep& pr, u32 d, u32 l
     return kLane ? (u32)__builtin_popcount(K) : wave_sum((u32)__builtin_popcount(K));
 }
 
-// Decoded bytes of a non-tail tile of a literal stream, for every entry phase at once (round 6,
-// the summary pass is VALU-bound, 137 VALU per random tile, profiles/
-// r6bd_seg_sq_kinds.md).  Let EQ(j) be y[j] == y[j + 1].  When every EQ position j also has
-// y[j + 1] != y[j + 2] and y[j + 2] == '2', then (whatever the entry phase d):
-//   * no byte '2' is EQ (y[j + 1] would be '2' and differ from y[j + 2] == '2');
-//   * from d on, every EQ position is a token start, i.e. a "v v 2" pair: the pair's second byte
-//     is not EQ (y[j + 1] != y[j + 2]) nor is its '2', so nothing inside a pair is EQ, and a byte is
-//     a one-byte token exactly where it is neither EQ nor inside a pair;
-//   * positions 0 and 1 are required not EQ: below d they hold the end of a pair the previous tile
-//     started, whose digit may be anything;
-// so the tile decodes to (1008 - #EQ) - d + e bytes and leaves exit phase e = 2 / 1 / 0 for a pair
-// at 1007 / 1006 / neither, the same for every d.  No phase table, no phase scan.  Returns the
-// lane's count of non-EQ positions (0 on the lookahead lane) and e, or kNotFast when a position
-// breaks the condition (the caller then takes dec_prepare and the general path).
-constexpr u32 kEqBad = (~0xF0u & (~0xCCu | 0xAAu)) & 0xFFu;   // bitop3: ~a & (~b | c)
-__device__ __forceinline__ u32 dec_count_phasefree(const u32x4 cur, u32 lane, const DecK& kc, u32& e) {
-    constexpr uint64_t kOwned = (1ull << kOwnLanes) - 1ull;
-    const u32 w[4] = {cur.x, cur.y, cur.z, cur.w};
-    const u32 la = from_next_lane(w[0], 0u);
-    const u32 nb[4] = {alignbyte(w[1], w[0], 1), alignbyte(w[2], w[1], 1), alignbyte(w[3], w[2], 1),
-                       alignbyte(la, w[3], 1)};
-    const u32 dg[4] = {alignbyte(w[1], w[0], 2), alignbyte(w[2], w[1], 2), alignbyte(w[3], w[2], 2),
-                       alignbyte(la, w[3], 2)};
-    const u32 K80 = kc.K80, K7F = kc.K7F;
-    u32 ne[4];   // 0x80 per byte: y[j] != y[j + 1]
-#pragma unroll
-    for (u32 k = 0; k < 4; ++k) {
-        const u32 t = w[k] ^ nb[k];
-        ne[k] = bitop3<kOrAnd>(faddi<0x7F7F7F7Fu>(t & K7F), t, K80);
-    }
-    const u32 nn = from_next_lane(ne[0], K80);   // the next lane's first positions
-    u32 bad = 0u, cnt = 0u;
-#pragma unroll
-    for (u32 k = 0; k < 4; ++k) {
-        const u32 nen = alignbyte(k < 3u ? ne[k + 1u] : nn, ne[k], 1);   // y[j + 1] != y[j + 2]
-        const u32 b = dg[k] ^ 0x32323232u;
-        const u32 nd = bitop3<kOrAnd>(faddi<0x7F7F7F7Fu>(b & K7F), b, K80);   // y[j + 2] != '2'
-        bad |= bitop3<kEqBad>(ne[k], nen, nd);   // EQ without NE(j + 1), or with a digit other than '2'
-        cnt += (u32)__builtin_popcount(ne[k]);
-    }
-    if (__builtin_amdgcn_ballot_w64((bad & K80) != 0u) & kOwned) return kNotFast;
-    if ((readlane(ne[0], 0) & 0x8080u) != 0x8080u) return kNotFast;   // EQ at position 0 or 1
-    const u32 ne62 = readlane(ne[3], kOwnLanes - 1u);   // positions 1004..1007
-    e = !(ne62 & 0x80000000u) ? 2u : (!(ne62 & 0x00800000u) ? 1u : 0u);
-    return lane < kOwnLanes ? cnt : 0u;
-}
-
-// One segment's decode summary: for each entry phase 0..2, the decoded bytes (.x .y .z) and, in .w,
-// the exit phases (2 bits each) and the phases whose tiled path declines (bits 8..10).  C > 0.
 // Whether every token starting in this tile (entry phase d, starts S80 from dec_lengths) carries
 // one byte v, the byte of the tile's first token.
 __device__ __forceinline__ bool dec_tile_single(const DecPrep& pr, const DecLen& ln, u32 d, const DecK& kc, u32& v) {
@@ -544,7 +215,6 @@ __device__ __forceinline__ bool dec_tile_single(const DecPrep& pr, const DecLen&
 // the exit phases (2 bits each), the phases whose tiled path declines (bits 8..10) and the phases
 // from which every token carries one byte (bits 11..13: the segment decodes to copies of that byte,
 // the one at its first token; dec_seg_fill writes them without reading the segment).  C > 0.
-template <bool kRes = false>
 __device__ __forceinline__ uint4 dec_seg_summarize(const uint8_t* src, u32 C, u32 q0, u32 q1, u32 lane,
                                                    const uint8_t* slots, const DecEntry* tbl) {
     const u32x4 rsi = make_rsrc(src, (C + 15u) & ~15u);
@@ -552,33 +222,11 @@ __device__ __forceinline__ uint4 dec_seg_summarize(const uint8_t* src, u32 C, u3
     u32 uni = 7u, v0 = 0u, v1 = 0u, v2 = 0u;   // single-byte phases and their bytes
     u32 accm = 0u;       // the lane's decoded bytes over the tiles after the phases merged (summed once)
     bool badl = false;   // ... and whether the lane declined in one of them
-    u32 a0 = 0u, a1 = 0u, a2 = 0u;   // phase-free tiles: e - d per entry phase (wave-uniform, wrapping)
-    constexpr u32 kPfWait = RLE_SEG_PF_WAIT;
-    u32 pf_wait = 0u;
     const DecK kc = dec_k();
-    walk_seg<kRes>(rsi, q0, ntiles_for(q1 - q0), lane, slots, [&](u32 t, const uint8_t* cs, const Refill& nx) {
+    walk_seg(rsi, q0, ntiles_for(q1 - q0), lane, slots, [&](u32 t, const uint8_t* cs, const Refill& nx) {
         const u32x4 cur = *reinterpret_cast<const u32x4*>(cs + 16u * lane);
         nx();
         const u32 pos = q0 + t * kTileStep;
-        // (dec_prepare's non-tail tiles; after a tile the check declines, the next kPfWait tiles go
-        // straight to the general path: run-heavy and zero-filled streams decline on every tile,
-        // r6be: runs50 summary 276.5 -> 364.9 µs when every tile tried)
-        if (pf_wait) {
-            --pf_wait;
-        } else if (RLE_SEG_PHASEFREE && pos + kSlot + 2u <= q1) {
-            u32 e = 0u;
-            const u32 tot = dec_count_phasefree(cur, lane, kc, e);
-            if (tot == kNotFast) pf_wait = kPfWait;
-            else {
-                accm += tot;
-                a0 += e - d0;
-                a1 += e - d1;
-                a2 += e - d2;
-                d0 = d1 = d2 = e;
-                uni = 0u;   // (as the literal path below)
-                return 0u;
-            }
-        }
         const DecPrep pr = dec_prepare(cur, pos, C, q1, lane, tbl, kc);
         const u32 m63 = readlane(pr.incl, kOwnLanes - 1u);   // lane 63: lookahead only
         if (d0 == d1 && d1 == d2) {   // the three entry phases have merged: one evaluation
@@ -629,7 +277,7 @@ __device__ __forceinline__ uint4 dec_seg_summarize(const uint8_t* src, u32 C, u3
         return 0u;
     });
     const u32 cm = wave_sum(accm);
-    c0 += cm + a0; c1 += cm + a1; c2 += cm + a2;
+    c0 += cm; c1 += cm; c2 += cm;
     badm |= __builtin_amdgcn_ballot_w64(badl) ? 7u : 0u;
     return make_uint4(c0, c1, c2, d0 | (d1 << 2) | (d2 << 4) | (badm << 8) | (uni << 11));
 }
@@ -664,8 +312,7 @@ __global__ __launch_bounds__(kSegBlock) void dec_seg_summary_kernel(const uint8_
 // The carried state of a decode scan over a buffer's segments: the entry phase, the output offset
 // and whether the buffer needs the exact serial path (a taken phase declines, or the stream decodes
 // past U).  One window of up to 64 consecutive segments (lane i: segment base + i, summary sm); each
-// lane gets its segment's entry phase and output offset; c advances past the window.  Shared by the
-// per-buffer scan and the single-pass kernel's look-back.
+// lane gets its segment's entry phase and output offset; c advances past the window.
 struct DecCarry {
     u32 e, off;
     bool serial;
@@ -777,7 +424,7 @@ __device__ RLE_SEG_UNIFORM_ATTR void dec_seg_fill(uint8_t* dst, u32 U, u32 off, 
 
 // One segment's output: the tile walk from entry phase e and output offset off; the stream's last
 // segment (last) also writes the bytes up to U and the status (st_b, when given).
-template <bool kRes, u32 kChunks>
+template <u32 kChunks>
 __device__ __forceinline__ void dec_seg_write(const uint8_t* src, uint8_t* dst, u32 C, u32 U, u32 q0, u32 q1, u32 e,
                                               u32 off, bool last, u32 lane, const uint8_t* slots, uint8_t* stage,
                                               const DecEntry* tbl, const u32x4* clut, uint32_t* st_b) {
@@ -785,7 +432,7 @@ __device__ __forceinline__ void dec_seg_write(const uint8_t* src, uint8_t* dst, 
     const u32x4 rso = make_rsrc(dst, U);
     DecState st{off, off & ~15u, e, 0u, 0u, off & 15u, 0u, false, {}};
     const DecK kc = dec_k();
-    const bool serial = walk_seg<kRes>(rsi, q0, ntiles_for(q1 - q0), lane, slots, [&](u32 t, const uint8_t* cs, const Refill& nx) {
+    const bool serial = walk_seg(rsi, q0, ntiles_for(q1 - q0), lane, slots, [&](u32 t, const uint8_t* cs, const Refill& nx) {
         // the fast tile paths (round 3): past the segment's shared first chunk, and the literal
         // path only on tiles a later tile of this segment follows (dec_tile)
         return dec_tile<true, kChunks, false>(cs, nx, q0 + t * kTileStep, C, q1, U, lane, tbl, stage, dst, rso, st, kc,
@@ -850,8 +497,8 @@ __global__ __launch_bounds__(kSegBlock) void dec_seg_write_kernel(const uint8_t*
                 return;
             }
         }
-        dec_seg_write<false, kSegDecChunks>(src, dst, C, U, q0, q1, uniform(pl.x), uniform(pl.y), g + 1u == s0 + nseg,
-                                            lane, slots, stage, tbl, clut, status ? status + b : nullptr);
+        dec_seg_write<kSegDecChunks>(src, dst, C, U, q0, q1, uniform(pl.x), uniform(pl.y), g + 1u == s0 + nseg,
+                                     lane, slots, stage, tbl, clut, status ? status + b : nullptr);
     });
 }
 
@@ -928,137 +575,10 @@ __global__ __launch_bounds__(kSegBlock) void dec_seg_write_packed_kernel(const u
                 return;
             }
         }
-        dec_seg_write<false, kSegDecChunks>(src, base, C, E, q0, q1, uniform(pl.x), off, g + 1u == s0 + nseg, lane, slots,
-                                            stage, tbl, clut, status ? status + b : nullptr);
+        dec_seg_write<kSegDecChunks>(src, base, C, E, q0, q1, uniform(pl.x), off, g + 1u == s0 + nseg, lane, slots,
+                                     stage, tbl, clut, status ? status + b : nullptr);
     });
 }
-
-
-#if RLE_VARIANTS
-// ---------------------------------------------------------------- resident single-pass decode
-// The decode form of enc_seg_res_kernel: a segment's summary is its three entry phases' counts and
-// exits (dec_seg_summarize), its entering phase and offset come from the look-back (dec_seg_window
-// over the published summaries), and its output walk reads the same LDS tiles.  A buffer that needs
-// the exact serial path (a taken phase declines, the stream decodes past U, or a look-back ran out
-// of polls) is only known once its last segment has combined: its segments skip their walks from
-// the first one that knows, the buffer is flagged (bflag, cleared by the plan), and
-// dec_seg_serial_kernel decodes it after this launch, over whatever the earlier segments wrote.
-// kRes false (RLE_MI355X_SEG_RES=2, round 5): the same single pass without the LDS-resident segment
-// (its 28 KB region per workgroup capped it at 3 workgroups per CU): the summary walks the segment
-// through the two DMA slots, and the write walks it again, from the caches if it is still there.
-template <bool kRes>
-__global__ __launch_bounds__(kSegBlock) void dec_seg_res_kernel(const uint8_t* __restrict__ in,
-                                                                const uint64_t* __restrict__ in_off,
-                                                                const uint64_t* __restrict__ in_len,
-                                                                uint8_t* __restrict__ out,
-                                                                const uint64_t* __restrict__ out_off,
-                                                                const uint64_t* __restrict__ out_len,
-                                                                const uint64_t* __restrict__ out_cap,
-                                                                uint32_t* __restrict__ status, u32 n,
-                                                                const u32* __restrict__ seg_first,
-                                                                const u32* __restrict__ seg_buf, u32 maxseg, u32 sb,
-                                                                uint4* __restrict__ summ, uint4* __restrict__ incl,
-                                                                u32* __restrict__ sflag, u32* __restrict__ ticket,
-                                                                u32* __restrict__ bflag) {
-    constexpr u32 kStage = 32u * kResDecChunks;
-    constexpr u32 kRegion = kRes ? kResStride : 2u * kSlot;   // the resident segment, or two DMA slots
-    __shared__ __attribute__((aligned(16))) uint8_t region_all[kSegWaves * kRegion];
-    __shared__ __attribute__((aligned(128))) uint8_t stage_all[kSegWaves * kStage];
-    __shared__ DecEntry tbl[256];
-    __shared__ u32x4 clut[kCompactEntries];   // dec_tile_fast's selectors
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = uniform(threadIdx.x / kWave);
-    for (u32 k = threadIdx.x; k < 256u; k += kSegBlock) tbl[k] = dec_entry_from(kDecTable.e[k]);
-    for (u32 k = threadIdx.x; k < kCompactEntries; k += kSegBlock)
-        clut[k] = u32x4{kCompactLut.s[4u * k], kCompactLut.s[4u * k + 1u], kCompactLut.s[4u * k + 2u],
-                        kCompactLut.s[4u * k + 3u]};
-    uint8_t* stage = stage_all + wid * kStage;
-    const uint8_t* region = region_all + wid * kRegion;
-    for (u32 k = lane; k < kStage / 16u; k += kWave) reinterpret_cast<u32x4*>(stage)[k] = u32x4{0u, 0u, 0u, 0u};
-    __syncthreads();
-    u32 total = uniform(seg_first[n]);
-    total = total < maxseg ? total : maxseg;
-    (void)ticket;
-    u32 gnext = blockIdx.x * kSegWaves + wid;   // one segment per wave
-    for (;;) {
-        const u32 g = uniform(gnext);
-        if (g >= total) break;
-        gnext = total;
-        {
-            const u32 b = uniform(seg_buf[g]);
-            const u32 s0 = uniform(seg_first[b]), s1 = uniform(seg_first[b + 1]), nseg = s1 - s0;
-            const uint64_t C64 = in_len[b], U64 = out_len[b];
-            const uint64_t cap = out_cap ? out_cap[b] : U64;
-            const uint8_t* src = in + in_off[b];
-            uint8_t* dst = out + out_off[b];
-            u32 bad = ((((uintptr_t)src | (uintptr_t)dst) & 15u) || cap < U64) ? RLE_STATUS_MISALIGNED : 0u;
-            if (C64 > kMaxBufferBytes || U64 > kMaxBufferBytes || s1 > maxseg) bad |= RLE_STATUS_TOOLARGE;
-            if (bad) {   // the buffer's segments all skip
-                if (g == s0 && lane == 0 && status) status[b] = bad;
-                continue;
-            }
-            const u32 C = (u32)C64, U = (u32)U64;
-            u32 q0, q1;
-            seg_range(g - s0, nseg, C, sb, q0, q1);
-            uint4 sm = kDecEmpty;
-            if (C) {
-                if (kRes) res_load(make_rsrc(src, (C + 15u) & ~15u), q0, ntiles_for(q1 - q0), lane, region);
-                sm = dec_seg_summarize<kRes>(src, C, q0, q1, lane, region, tbl);
-            }
-            if (lane == 0) publish(summ + g, sm, sflag + g, kFlagAgg);
-            bool late = false;
-            DecCarry c{0u, 0u, false};
-            if (g > s0) {
-                const u32 from = seg_lookback(g, s0, sflag, lane, late);
-                if (from > s0) {
-                    const uint4 in4 = ld_relaxed4(incl + (from - 1u));
-                    c = DecCarry{uniform(in4.x), uniform(in4.y), uniform(in4.z) != 0u};
-                }
-                for (u32 base = from; base < g; base += kWave) {
-                    const u32 j = base + lane;
-                    const bool valid = j < g;
-                    const uint4 smj = valid ? ld_relaxed4(summ + j) : make_uint4(0u, 0u, 0u, 0u);
-                    dec_seg_window(smj, valid, U, c);
-                }
-            }
-            const uint2 mine = dec_seg_window(sm, lane == 0u, U, c);
-            c.serial = c.serial || late;
-            const bool last = g + 1u == s1;
-            if (lane == 0) {
-                publish(incl + g, make_uint4(c.e, c.off, c.serial ? 1u : 0u, 0u), sflag + g, kFlagIncl);
-                // the buffer's serial flag: from its last segment, or from any segment whose
-                // look-back ran out (its state may not reach the last segment's combine)
-                if ((last && c.serial) || late) atomicOr(bflag + b, kFlagSerial);
-            }
-            if (!c.serial)
-                dec_seg_write<kRes, kResDecChunks>(src, dst, C, U, q0, q1, uniform(mine.x), uniform(mine.y), last, lane,
-                                                   region, stage, tbl, clut, status ? status + b : nullptr);
-        }
-    }
-}
-
-// After dec_seg_res_kernel: the exact serial decode of the buffers it flagged, one wave each.
-__global__ __launch_bounds__(kSegBlock) void dec_seg_serial_kernel(const uint8_t* __restrict__ in,
-                                                                   const uint64_t* __restrict__ in_off,
-                                                                   const uint64_t* __restrict__ in_len,
-                                                                   uint8_t* __restrict__ out,
-                                                                   const uint64_t* __restrict__ out_off,
-                                                                   const uint64_t* __restrict__ out_len,
-                                                                   const uint64_t* __restrict__ out_cap,
-                                                                   uint32_t* __restrict__ status, u32 n,
-                                                                   const u32* __restrict__ bflag) {
-    __shared__ __attribute__((aligned(16))) uint8_t stage_all[kSegWaves * 1024];
-    const u32 lane = threadIdx.x & (kWave - 1);
-    const u32 wid = uniform(threadIdx.x / kWave);
-    const u32 b = blockIdx.x * kSegWaves + wid;
-    if (b >= n || !(uniform(bflag[b]) & kFlagSerial)) return;
-    const u32 U = (u32)out_len[b];
-    const uint64_t cap = out_cap ? out_cap[b] : (uint64_t)U;
-    const u32 stat = dec_serial(in + in_off[b], (u32)in_len[b], U, cap, out + out_off[b], lane, stage_all + wid * 1024, 1024);
-    if (lane == 0 && status) status[b] = stat;
-}
-
-#endif  // RLE_VARIANTS
 
 }  // namespace rle
 
@@ -1100,35 +620,9 @@ inline uint32_t max_segments(uint32_t n, uint64_t total, uint32_t sb) {
     const uint64_t m = total / (sb - 2u) + n;
     return m > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)m;
 }
-#if RLE_VARIANTS   // (the product build reads neither variable)
-// RLE_MI355X_SEG_RES: 0 off, 1 the resident single pass (enc_seg_res_kernel / dec_seg_res_kernel),
-// 2 the single pass without the resident segment (decode)
-int seg_res_mode() {
-    static const int m = [] {
-        const char* e = getenv("RLE_MI355X_SEG_RES");
-        return e ? atoi(e) : 0;
-    }();
-    return m;
-}
-// the fused single-pass encode (RLE_MI355X_SEG_FUSED=1; measured slower than the four launches, §4)
-bool seg_fused() {
-    static const bool on = [] {
-        const char* e = getenv("RLE_MI355X_SEG_FUSED");
-        return e ? e[0] != '0' : false;
-    }();
-    return on;
-}
-#endif
 // segment length in bytes: about 16 segments per CU over the batch, 4..16 tiles each
 // (longer segments, caps of 32 / 64 tiles, measured slower on the mixed batch: r5w)
-// The resident kernels' segments are one tile shorter than an LDS region, so that a buffer's last
-// segment (which absorbs a remainder of up to 2 bytes) still fits.  Segment lengths stay whole
-// tiles: a segment's exit state is read after the last tile's last lane (an 8048-byte segment,
-// measured, left the decode exit phase one lane late).
 inline uint32_t seg_bytes(uint64_t total, int ncu) {
-#if RLE_VARIANTS
-    if (seg_res_mode() == 1) return (rle::kResTiles - 1u) * rle::kTileStep;
-#endif
     const uint64_t tiles = (total + rle::kTileStep - 1) / rle::kTileStep;
     uint64_t per = tiles / ((uint64_t)ncu * 16u);
     per = per < rle::kSegTilesMin ? rle::kSegTilesMin : (per > rle::kSegTilesMax ? rle::kSegTilesMax : per);
@@ -1145,8 +639,7 @@ inline uint32_t seg_grid(uint32_t maxseg, int ncu) {
     const uint32_t g = need < fill ? need : fill;
     return g ? g : 1u;
 }
-// The launch shape: segment length, segment bound, grid, and the carve-up of the workspace at base
-// (the three single-pass tables are carved in every build: the size is part of the contract).
+// The launch shape: segment length, segment bound, grid, and the carve-up of the workspace at base.
 rle::SegShape seg_shape(char* base, uint32_t n, uint64_t total, int ncu, size_t extra) {
     rle::SegShape sh;
     sh.ncu = ncu;
@@ -1165,9 +658,8 @@ rle::SegShape seg_shape(char* base, uint32_t n, uint64_t total, int ncu, size_t 
     sh.summ = reinterpret_cast<uint4*>(take(sizeof(uint4) * m));
     sh.plan = reinterpret_cast<uint2*>(take(sizeof(uint2) * m));
     sh.bflag = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * (size_t)n));
-    sh.sflag = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * m));
-    sh.incl = reinterpret_cast<uint4*>(take(sizeof(uint4) * m));
-    sh.ticket = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t)));
+    // reserved, unused: three retired tables whose bytes stay in the published workspace size
+    take(al(sizeof(uint32_t) * m) + al(sizeof(uint4) * m) + al(sizeof(uint32_t)));
     sh.extra = take(extra);
     sh.bytes = o;
     return sh;
@@ -1184,11 +676,9 @@ int seg_prologue(void* d_workspace, size_t workspace_bytes, uint32_t n, uint64_t
     if (n == 1u) sh->seg_first = sh->seg_buf = nullptr;
     return RLE_OK;
 }
-void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hipStream_t s, uint32_t* sflag,
-                         uint32_t* ticket, uint32_t* bclear) {
+void seg_launch_plan_map(const uint64_t* len, uint32_t n, const SegShape& sh, hipStream_t s) {
     if (!sh.seg_first) return;
-    hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(1024), 0, s, len, n, sh.sb, sh.seg_first, sflag, sh.maxseg, ticket,
-                       bclear);
+    hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(1024), 0, s, len, n, sh.sb, sh.seg_first);
     hipLaunchKernelGGL(seg_map_kernel, dim3((sh.maxseg + kMapBlock - 1) / kMapBlock), dim3(kMapBlock), 0, s,
                        sh.seg_first, n, sh.maxseg, sh.seg_buf);
 }
@@ -1223,26 +713,6 @@ extern "C" int rle_encode_batch_device_seg(const void* d_in, const uint64_t* d_i
     const hipStream_t s = (hipStream_t)stream;
     const uint8_t* in = (const uint8_t*)d_in;
     uint8_t* out = (uint8_t*)d_out;
-#if RLE_VARIANTS
-    // (the single-pass kernels take the tables for one buffer too; their plan clears the status
-    // words: the segments OR into them)
-    if (seg_res_mode() == 1 || seg_fused()) sh = seg_shape(static_cast<char*>(d_workspace), n, total_in_bytes, sh.ncu, 0);
-    if (seg_res_mode() == 1) {
-        rle::seg_launch_plan_map(d_in_len, n, sh, s, sh.sflag, sh.ticket, d_status);
-        hipLaunchKernelGGL(rle::enc_seg_res_kernel, dim3(rle::seg_buf_grid(sh.maxseg)), dim3(rle::kSegBlock), 0, s, in,
-                           d_in_off, d_in_len, out, d_out_off, d_out_len, d_status, n, sh.seg_first, sh.seg_buf,
-                           sh.maxseg, sh.sb, sh.summ, sh.incl, sh.sflag, sh.ticket);
-        return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
-    }
-    if (seg_fused()) {   // (finds a segment's buffer by binary search: the plan alone, no map)
-        hipLaunchKernelGGL(rle::seg_plan_kernel, dim3(1), dim3(1024), 0, s, d_in_len, n, sh.sb, sh.seg_first, sh.sflag,
-                           sh.maxseg, sh.ticket, d_status);
-        hipLaunchKernelGGL(rle::enc_seg_fused_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len,
-                           out, d_out_off, d_out_len, d_status, n, sh.seg_first, sh.maxseg, sh.sb, sh.summ, sh.incl,
-                           sh.sflag, sh.ticket);
-        return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
-    }
-#endif
     rle::seg_launch_plan_map(d_in_len, n, sh, s);
     hipLaunchKernelGGL(rle::enc_seg_summary_kernel, dim3(sh.grid), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len,
                        n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb, sh.summ);
@@ -1266,19 +736,6 @@ extern "C" int rle_decode_batch_device_seg(const void* d_in, const uint64_t* d_i
     const hipStream_t s = (hipStream_t)stream;
     const uint8_t* in = (const uint8_t*)d_in;
     uint8_t* out = (uint8_t*)d_out;
-#if RLE_VARIANTS
-    if (seg_res_mode() == 1 || seg_res_mode() == 2) {   // (the tables for one buffer too)
-        sh = seg_shape(static_cast<char*>(d_workspace), n, total_in_bytes, sh.ncu, 0);
-        rle::seg_launch_plan_map(d_in_len, n, sh, s, sh.sflag, sh.ticket, sh.bflag);
-        hipLaunchKernelGGL(seg_res_mode() == 1 ? rle::dec_seg_res_kernel<true> : rle::dec_seg_res_kernel<false>,
-                           dim3(rle::seg_buf_grid(sh.maxseg)), dim3(rle::kSegBlock), 0, s, in, d_in_off, d_in_len, out,
-                           d_out_off, d_out_len, d_out_cap, d_status, n, sh.seg_first, sh.seg_buf, sh.maxseg, sh.sb,
-                           sh.summ, sh.incl, sh.sflag, sh.ticket, sh.bflag);
-        hipLaunchKernelGGL(rle::dec_seg_serial_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, in,
-                           d_in_off, d_in_len, out, d_out_off, d_out_len, d_out_cap, d_status, n, sh.bflag);
-        return hipGetLastError() == hipSuccess ? RLE_OK : RLE_E_HIP;
-    }
-#endif
     rle::seg_launch_plan_map(d_in_len, n, sh, s);
     rle::seg_launch_dec_summary(in, d_in_off, d_in_len, n, sh, s);
     hipLaunchKernelGGL(rle::dec_seg_scan_kernel, dim3(rle::seg_buf_grid(n)), dim3(rle::kSegBlock), 0, s, in, d_in_off,

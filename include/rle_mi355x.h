@@ -156,8 +156,8 @@ typedef struct {
     uint64_t bytes_in, bytes_out, bytes_h2d, bytes_d2h;
     uint64_t ns_stage_in, ns_device, ns_stage_out;
     uint64_t calls_append;   /* RLEappend (include/rle_fileops.h); RLEdecompressN counts per file */
-    uint64_t calls_coalesced, launches_coalesced;   /* zero-copy small calls and the combined launches
-                                                       they ran in (concurrent callers share one) */
+    uint64_t calls_coalesced, launches_coalesced;   /* always 0: call coalescing is retired, the layout
+                                                       stays */
     uint64_t calls_registered;     /* large calls run on the caller's registered memory (RLE_MI355X_REG_MIN) */
     uint64_t calls_reg_fallback;   /* ... and those that took the staging instead (registration refused or
                                       overlapping another call's) */

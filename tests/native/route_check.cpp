@@ -1,6 +1,6 @@
 // route_check — prints the drop-in's route (csrc/rle_route.h) for sizes and settings read from stdin,
 // one query per line (tests/test_route.py):
-//   [zerocopy=0|1] [zc_seg=N] [zc_coop=0|1] [reg_min=N] [fake_devs=N] [coalesce=0|1] [service=0|1] then
+//   [zerocopy=0|1] [zc_seg=N] [zc_coop=0|1] [reg_min=N] [fake_devs=N] then
 //   compress U | decompress C U E | append C U A MAX_WHOLE MAX_TAIL | readn C U
 // (MAX_WHOLE / MAX_TAIL: rle_max_compressed_size(U + A) / (16 + A), which the library defines).
 #include <stdio.h>
@@ -13,8 +13,6 @@ static const char* body_name(rle::Body b) {
     switch (b) {
     case rle::Body::MappedOne: return "mapped_one";
     case rle::Body::MappedSeg: return "mapped_seg";
-    case rle::Body::MappedCoalesce: return "mapped_coalesce";
-    case rle::Body::MappedService: return "mapped_service";
     case rle::Body::Staged: return "staged";
     case rle::Body::Large: return "large";
     }
@@ -40,8 +38,6 @@ int main() {
                 else if (!strcmp(tok, "zc_coop")) s.zc_coop = x != 0;
                 else if (!strcmp(tok, "reg_min")) s.reg_min = (size_t)x;
                 else if (!strcmp(tok, "fake_devs")) s.fake_devs = (int)x;
-                else if (!strcmp(tok, "coalesce")) s.coalesce = x != 0;
-                else if (!strcmp(tok, "service")) s.service = x != 0;
                 else return 2;
             } else if (!op) {
                 op = tok;

@@ -38,7 +38,7 @@ NPROBES = 16
 NKINDS = 4
 TILE = 1008            # owned stream bytes of one decode tile
 SEG = 64512            # a common multiple of the four-launch kernels' 4-, 8- and 16-tile segments
-SEG_RES = 7056         # segment length of the resident single-pass kernels
+SEG_RES = 7056         # 7-tile segments (tests/test_gpu_seg_lengths.py runs them); once the retired resident kernels' length
 _FILL = (0x71, 0x72, 0x73)   # q r s: literals no prefix alphabet pairs up and no probe value equals
 _CARRIER = 2 * SEG + 8192
 _MIXED = (0x61, 0x62, 0x35, 0x39, 0x00, 0x80, 0x7A)

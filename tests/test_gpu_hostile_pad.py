@@ -9,9 +9,6 @@ encoder its final run going on; with packed slots and a length that is a multipl
 buffer itself begins that way.  Both layouts run: packed, and 16 spare bytes after every slot.
 Expected outputs are the oracle's: O.encode(x), O.decode(stream, U, cap)."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import pytest
 
@@ -21,12 +18,7 @@ import stream_family as F
 from test_gpu_parity import gpu_decode, gpu_encode
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-PKG = os.path.join(ROOT, "c-filestorage-server-and-client_amd")
-TESTLIB = os.path.join(PKG, "build", "librle_mi355x_testhooks.so")
-RES = os.environ.get("RLE_MI355X_SEG_RES", "0") == "1"
-S = F.SEG_RES if RES else F.SEG
+S = F.SEG
 SIZES = [1, 2, 15, 16, 17, 1007, 1008, 1009, 1023, 1024, 1025, 2016, 4096, S - 1, S, S + 1]
 PADS = [0, 16]
 _cache = {}
@@ -125,28 +117,6 @@ def test_encode_cooperative(pad, always_coop):
 @pytest.mark.parametrize("pad", PADS)
 def test_seg_encode(pad):
     _check_encode(pad, seg=True)
-
-
-_ONE_PASS = r'''
-import sys
-sys.path[:0] = sys.argv[1:4]
-import rle_mi355x as R
-from test_gpu_hostile_pad import _check_encode, PADS
-for waves in (4, 16):
-    R.set_stream_waves(waves)
-    for pad in PADS:
-        _check_encode(pad, one_pass=True)
-print("ok")
-'''
-
-
-def test_encode_one_pass():
-    """The one-pass encode lives in the test library only: a fresh process on it."""
-    assert os.path.exists(TESTLIB), "build() makes the test library"
-    env = dict(os.environ, RLE_MI355X_LIB=TESTLIB)
-    r = subprocess.run([sys.executable, "-c", _ONE_PASS, PKG, os.path.join(ROOT, "oracle"), HERE], env=env,
-                       capture_output=True, text=True, timeout=110)
-    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
 
 
 # ------------------------------------------------------------------ decode

@@ -1,15 +1,14 @@
 """GPU tests of the drop-in's host path (BASELINE configs[4]).
 
 * The registered large calls (the default past the zero-copy reach) and every staging mode a call
-  falls back to (RLE_MI355X_STAGING = direct / pinned / pipe, read at library init: a fresh process
+  falls back to (RLE_MI355X_STAGING = direct / pinned, read at library init: a fresh process
   each) give the oracle's bytes for RLEcompress / RLEdecompress across the size thresholds
   (zero-copy small calls, pinned one-trip, segmented, >= 256 KiB), for RLEappend and for
   RLEdecompressN with a file past the staging cap; registered calls from eight threads on buffers
   that share pages, on one shared stream, on overlapping ranges and on read-only pages.
 * Concurrent small calls from many threads (the server's worker pool, src/server.c:520-524) stay
-  bit-exact, on per-thread streams (the default) and combined into shared launches
-  (RLE_MI355X_COALESCE=1): each thread's streams against the oracle, and the C call-rate tool's
-  round trips.
+  bit-exact on per-thread streams: each thread's streams against the oracle, and the C call-rate
+  tool's round trips.
 """
 import json
 import os
@@ -50,20 +49,13 @@ print("ok", R.dropin_stats())
 '''
 
 
-# call coalescing and pipelined staging are measured slower than the defaults and live only in the
-# test build (RLE_VARIANTS, c-filestorage-server-and-client_amd/Makefile), not in the product library
-VARIANTS_LIB = os.path.join(ROOT, "c-filestorage-server-and-client_amd", "build", "librle_mi355x_testhooks.so")
-
-
-@pytest.mark.parametrize("mode", ["registered", "direct", "pinned", "pipe"])
+@pytest.mark.parametrize("mode", ["registered", "direct", "pinned"])
 def test_staging_modes_bit_exact(mode):
     # "registered" is the default (large calls on the caller's registered memory); the staging modes
     # are what a call falls back to, so they run with the registered path off
     env = dict(os.environ, RLE_MI355X_STAGE_CAP=str(1 << 20))
     if mode != "registered":
         env.update(RLE_MI355X_STAGING=mode, RLE_MI355X_REG_MIN="0")
-    if mode == "pipe":
-        env["RLE_MI355X_LIB"] = VARIANTS_LIB
     r = subprocess.run([sys.executable, "-c", _STAGING_CODE, os.path.join(ROOT, "c-filestorage-server-and-client_amd"),
                         os.path.join(ROOT, "oracle")], env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
@@ -215,54 +207,6 @@ def test_registered_calls_on_streams_the_encoder_never_writes():
         assert got == ref, (len(s), U, E)
 
 
-_COALESCE_CODE = r'''
-import sys, threading
-sys.path[:0] = sys.argv[1:3]
-import rle_mi355x as R, rle_oracle as O
-R.dropin_stats(reset=True)
-errors = []
-inputs = [[O.gen(k % 4, 7000 + 100 * t + k, 4096 + 9000 * (k % 5)) for k in range(40)] for t in range(16)]
-refs = [[O.encode(x) for x in xs] for xs in inputs]
-
-def work(t):
-    try:
-        for x, y in zip(inputs[t], refs[t]):
-            if R.compress(x) != y:
-                errors.append(("enc", t, len(x)))
-            if R.decompress(y, len(x), 3) != x + bytes(3):
-                errors.append(("dec", t, len(x)))
-    except Exception as e:   # surfaced below
-        errors.append(repr(e))
-
-th = [threading.Thread(target=work, args=(t,)) for t in range(16)]
-for x in th:
-    x.start()
-for x in th:
-    x.join()
-assert not errors, errors[:5]
-st = R.dropin_stats()
-# every compress is a zero-copy call (U < 48 KiB); decompress is from C < 32 KiB
-small = 16 * 40 + sum(len(y) < (32 << 10) for ys in refs for y in ys)
-assert st["calls_coalesced"] == small
-assert 0 < st["launches_coalesced"] <= st["calls_coalesced"]
-print("ok", st)
-'''
-
-
-def test_concurrent_small_calls_coalesced_bit_exact():
-    """With call coalescing on (RLE_MI355X_COALESCE=1, read at init: a fresh process): 16 Python
-    threads, each 40 round trips of its own 4 KiB - 40 KiB buffers through the drop-in, every stream
-    against the oracle; the library counts every small call as combined."""
-    # (no background start-up: its warm-up calls would be combined too, after the counters' reset)
-    # (and the one-wave zero-copy range only: the count below is of calls under 48 / 32 KiB)
-    # (coalescing combines zero-copy calls: RLE_MI355X_SMALL from the caller's environment is reset)
-    env = dict(os.environ, RLE_MI355X_COALESCE="1", RLE_MI355X_LIB=VARIANTS_LIB, RLE_MI355X_PREINIT="0",
-               RLE_MI355X_ZC_SEG="0", RLE_MI355X_SMALL="zerocopy")
-    r = subprocess.run([sys.executable, "-c", _COALESCE_CODE, os.path.join(ROOT, "c-filestorage-server-and-client_amd"),
-                        os.path.join(ROOT, "oracle")], env=env, capture_output=True, text=True, timeout=110)
-    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
-
-
 def test_concurrent_small_calls_per_thread_streams_bit_exact():
     """The default (one stream per calling thread, no combining): 16 threads of 4 KiB - 40 KiB round
     trips against the oracle, and no call was combined."""
@@ -372,66 +316,16 @@ print("ok")
 '''
 
 
-@pytest.mark.parametrize("poll,service,zcseg,one", [("1", "0", "0", "1"), ("0", "0", "0", "1"), ("1", "1", "0", "1"),
-                                                    ("1", "0", "8192", "1"), ("1", "0", "0", "0")])
-def test_polled_small_calls_bit_exact(poll, service, zcseg, one):
+@pytest.mark.parametrize("poll,zcseg,one", [("1", "0", "1"), ("0", "0", "1"), ("1", "8192", "1"), ("1", "0", "0")])
+def test_polled_small_calls_bit_exact(poll, zcseg, one):
     """The zero-copy small calls' completion: polling the status word the kernel stores behind a
-    system-scope release (RLE_MI355X_POLL=1, the default) or hipStreamSynchronize (=0), or the
-    resident service (RLE_MI355X_SERVICE=1: no launch per call, csrc/rle_service.h; built into the
-    RLE_VARIANTS test library only since round 5, so that case loads it).  600
+    system-scope release (RLE_MI355X_POLL=1, the default) or hipStreamSynchronize (=0).  600
     consecutive calls of 0-16 KiB (cooperative and one-wave kernels), decodes with an extra region,
     serial-path streams, then 8 threads x 150 round trips, all against the oracle.  zcseg: calls
     from that many bytes run the segmented kernels on the mapped buffer (RLE_MI355X_ZC_SEG).  one:
     the cooperative kernels take a single call's sizes as arguments (RLE_MI355X_COOP_ONE=1, the
     default since round 6) or read them from the mapped launch words (=0, the batched entry points)."""
-    env = dict(os.environ, RLE_MI355X_POLL=poll, RLE_MI355X_SERVICE=service, RLE_MI355X_ZC_SEG=zcseg,
-               RLE_MI355X_COOP_ONE=one)
-    if service == "1":
-        env["RLE_MI355X_LIB"] = VARIANTS_LIB
+    env = dict(os.environ, RLE_MI355X_POLL=poll, RLE_MI355X_ZC_SEG=zcseg, RLE_MI355X_COOP_ONE=one)
     r = subprocess.run([sys.executable, "-c", _POLL_CODE, os.path.join(ROOT, "c-filestorage-server-and-client_amd"),
-                        os.path.join(ROOT, "oracle")], env=env, capture_output=True, text=True, timeout=110)
-    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
-
-
-_SERVICE_CODE = r"""
-import sys, threading, time
-sys.path[:0] = sys.argv[1:3]
-import rle_mi355x as R, rle_oracle as O
-errors = []
-# calls spaced past the service's idle time (1 ms): every call finds it gone and relaunches it
-for k in range(20):
-    x = O.gen(k % 5, 500 + k, 1000 + 700 * k)
-    y = O.encode(x)
-    if R.compress(x) != y or R.decompress(y, len(x)) != x:
-        errors.append(("gap", k))
-    time.sleep(0.003)
-# many threads at once: one resident service workgroup each
-def work(t):
-    try:
-        for k in range(6):
-            U = 1 + (k * 3001 + t * 17) % 20000
-            x = O.gen((k + t) % 5, 70000 + 100 * t + k, U)
-            y = O.encode(x)
-            if R.compress(x) != y or R.decompress(y, U, 5) != x + bytes(5):
-                errors.append(("thread", t, k))
-    except Exception as e:
-        errors.append(repr(e))
-th = [threading.Thread(target=work, args=(t,)) for t in range(72)]
-for x in th:
-    x.start()
-for x in th:
-    x.join()
-assert not errors, errors[:5]
-print("ok")
-"""
-
-
-def test_service_relaunch_and_overflow_bit_exact():
-    """The resident service (RLE_MI355X_SERVICE=1) across its own idle exits (calls 3 ms apart: a
-    relaunch each) and with 72 threads at once (72 resident workgroups, one per thread context),
-    every stream against the oracle; the process then exits with every service stopped.  (The
-    service is built into the RLE_VARIANTS test library only.)"""
-    env = dict(os.environ, RLE_MI355X_SERVICE="1", RLE_MI355X_LIB=VARIANTS_LIB)
-    r = subprocess.run([sys.executable, "-c", _SERVICE_CODE, os.path.join(ROOT, "c-filestorage-server-and-client_amd"),
                         os.path.join(ROOT, "oracle")], env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])

@@ -15,9 +15,6 @@ the first, a middle and the last index of a batch of valid buffers, in every for
 
 Slots have 32 spare bytes, so a buffer shifted off its alignment stays inside its own slot."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -27,10 +24,6 @@ import rle_mi355x as R
 import rle_oracle as O
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-PKG = os.path.join(ROOT, "c-filestorage-server-and-client_amd")
-TESTLIB = os.path.join(PKG, "build", "librle_mi355x_testhooks.so")
 DEV = "cuda:0"
 POISON = 0xA5
 TILE = 1008
@@ -143,10 +136,6 @@ def _enc_flag(d_in, ioff, ilen, d_out, ooff, olen, st, mx):
     R.encode_batch(d_in, ioff, ilen, d_out, ooff, olen, st, max_len=mx, flags=R.RLE_LAUNCH_STATUS_FLAG)
 
 
-def _enc_stream(d_in, ioff, ilen, d_out, ooff, olen, st, mx):
-    R.encode_batch_stream(d_in, ioff, ilen, d_out, ooff, olen, st)
-
-
 def _enc_seg(d_in, ioff, ilen, d_out, ooff, olen, st, mx):
     R.encode_batch_seg(d_in, ioff, ilen, d_out, ooff, olen, st)
 
@@ -202,30 +191,6 @@ def test_sized_cooperative(always_coop):
 def test_sized_cooperative_status_flag(always_coop):
     """RLE_LAUNCH_STATUS_FLAG: the status word is stored last, over a preset no status takes."""
     _small_batch_forms(_enc_flag, _dec_flag, "cooperative, status flag", preset=-1)
-
-
-def stream_form():
-    """(the child of test_one_pass_encode_stream: rle_encode_stream_launch is in the test library)"""
-    xs = batch()
-    for r, bad in enumerate(rotations(len(xs), ENC_KINDS)):
-        encode_refusals(xs, bad, _enc_stream, f"one-pass stream encode, rotation {r}")
-
-
-_STREAM_CODE = r'''
-import sys
-sys.path[:0] = sys.argv[1:4]
-import test_gpu_refusals as T
-T.stream_form()
-print("ok")
-'''
-
-
-def test_one_pass_encode_stream():
-    assert os.path.exists(TESTLIB), "build() makes the test library"
-    env = dict(os.environ, RLE_MI355X_LIB=TESTLIB)
-    r = subprocess.run(["timeout", "-k", "10", "100", sys.executable, "-c", _STREAM_CODE, PKG,
-                        os.path.join(ROOT, "oracle"), HERE], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ok" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
 
 
 def test_segmented_many_buffers():

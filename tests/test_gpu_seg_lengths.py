@@ -16,10 +16,6 @@ Every test asserts, through rle_seg_segment_bytes, the length it ran at, so a de
 CU count fails there and not silently at other edges.  Outputs are compared byte for byte with the
 oracle, slots poisoned (seg_encode / seg_decode below: test_gpu_parity's launches with the hint);
 encode status 0, decode status without error bits."""
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
@@ -30,14 +26,8 @@ from test_gpu_parity import DEV, POISON, _i64, _input_image
 from test_gpu_stream_family import check
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-PKG = os.path.join(ROOT, "c-filestorage-server-and-client_amd")
-TESTLIB = os.path.join(PKG, "build", "librle_mi355x_testhooks.so")
 TILE = F.TILE
 LENGTHS = list(range(4, 17))
-if os.environ.get("RLE_MI355X_SEG_RES", "0") == "1":   # the resident variants have one fixed length
-    pytest.skip("per-length tests do not apply to the resident single pass", allow_module_level=True)
 
 
 def hint_for(m):
@@ -203,29 +193,3 @@ def test_dropin_files_between_20_and_64_mib(m, d, kind, dec_tiles):
         assert R.decompress(y, len(x), 5) == x + bytes(5)
     else:
         assert R.decompress(y, len(x)) == x
-
-
-def encode_every_length():
-    """The encode cases of every length in this process (the fused child below)."""
-    for m in LENGTHS:
-        cases = flat(valid_cases(m))
-        _encode_check(m, hint_for(m), cases, [O.encode(x) for _, _, x in cases])
-
-
-_FUSED_CODE = r'''
-import sys
-sys.path[:0] = sys.argv[1:4]
-import test_gpu_seg_lengths as T
-T.encode_every_length()
-print("ok")
-'''
-
-
-def test_fused_single_pass_encode_every_length():
-    """The fused single-pass encode (RLE_MI355X_SEG_FUSED=1 on the test library, read at load: a
-    fresh process) takes its segment length from the hint as well: this module's encode cases."""
-    assert os.path.exists(TESTLIB), "build() makes the test library"
-    env = dict(os.environ, RLE_MI355X_SEG_FUSED="1", RLE_MI355X_LIB=TESTLIB)
-    r = subprocess.run(["timeout", "-k", "10", "100", sys.executable, "-c", _FUSED_CODE, PKG,
-                        os.path.join(ROOT, "oracle"), HERE], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ok" in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])

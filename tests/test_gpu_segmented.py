@@ -6,8 +6,6 @@ segment lengths, so on segment edges (every other length: tests/test_gpu_seg_len
 '9' runs, whose decode phases never re-synchronise), mix buffer sizes, and feed invalid streams
 that must fall back to the exact serial decoder.  The algebra itself is pinned on CPU by
 tests/test_seg_model.py."""
-import os
-
 import numpy as np
 import pytest
 
@@ -16,21 +14,16 @@ import rle_oracle as O
 from test_gpu_parity import gpu_decode, gpu_encode
 
 pytestmark = pytest.mark.gpu
-# S: a multiple of the segment length of the path under test.  64512 is a common multiple of the 4-,
-# 8- and 16-tile segments (4032, 8064, 16128 bytes) the four-launch kernels take at these batch
-# sizes (_parity asserts it of every launch); the resident single-pass kernels
-# (RLE_MI355X_SEG_RES=1, which test_resident_single_pass below sets for a second run of this
-# module) have segments of exactly 7056 bytes (7 tiles)
-RES = os.environ.get("RLE_MI355X_SEG_RES", "0") == "1"
-RES_MODE = os.environ.get("RLE_MI355X_SEG_RES", "0")   # "2": the single pass without the resident segment
-S = 7056 if RES else 64512
+# S: a multiple of the segment length.  64512 is a common multiple of the 4-, 8- and 16-tile segments
+# (4032, 8064, 16128 bytes) the kernels take at these batch sizes (_parity asserts it of every launch)
+S = 64512
 
 
 def _edges_are_segment_edges(total_in_bytes):
-    """The launch of this many input bytes has segments that S is a multiple of (the resident run:
-    segments of S bytes), so the cases placed around k * S sit on segment edges."""
+    """The launch of this many input bytes has segments that S is a multiple of, so the cases placed
+    around k * S sit on segment edges."""
     sb = R.seg_segment_bytes(total_in_bytes)
-    assert sb == S if RES else S % sb == 0, (total_in_bytes, sb, S)
+    assert S % sb == 0, (total_in_bytes, sb, S)
 
 
 def _parity(xs):
@@ -161,62 +154,3 @@ def test_dropin_very_large_file():
     y = R.compress(x)
     assert y == O.encode(x)
     assert R.decompress(y, len(x)) == x
-
-
-_FUSED_CODE = r'''
-import sys
-sys.path[:0] = sys.argv[1:4]
-import rle_oracle as O
-from test_gpu_segmented import S
-from test_gpu_parity import gpu_encode
-xs = [bytes(3 * S + 5), O.gen(1, 1, 5 * S + 7), O.gen(2, 2, 2 * S), b"q" * (4 * S + 1), b"", b"a"]
-xs += [O.gen(k % 5, 40 + k, (k + 1) * 7000) for k in range(40)]
-xs.append(O.gen(3, 9, 64 << 20))   # one buffer of thousands of segments (the longest look-back)
-ys, st = gpu_encode(xs, seg=True)
-assert (st == 0).all(), st
-for i, x in enumerate(xs):
-    assert ys[i] == O.encode(x), (i, len(x))
-print("ok")
-'''
-
-
-def _variants_lib(root):
-    """The fused and resident kernels are measured slower than the default and live only in the test
-    build (RLE_VARIANTS, c-filestorage-server-and-client_amd/Makefile), not in the product library."""
-    p = os.path.join(root, "c-filestorage-server-and-client_amd", "build", "librle_mi355x_testhooks.so")
-    assert os.path.exists(p), "build() makes the test library"
-    return p
-
-
-def test_fused_single_pass_encode():
-    """The fused single-pass segmented encode (RLE_MI355X_SEG_FUSED=1, read at load: a fresh
-    process): ticket-ordered segments, write-through summaries and inclusive states, the decoupled
-    look-back, against the oracle -- including a 64 MiB buffer whose segments look back thousands
-    of places."""
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
-    env = dict(os.environ, RLE_MI355X_SEG_FUSED="1", RLE_MI355X_LIB=_variants_lib(root))
-    r = subprocess.run([sys.executable, "-c", _FUSED_CODE, os.path.join(root, "c-filestorage-server-and-client_amd"),
-                        os.path.join(root, "oracle"), here], env=env, capture_output=True, text=True, timeout=110)
-    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
-
-
-@pytest.mark.parametrize("mode", ["1", "2"])
-def test_resident_single_pass(mode):
-    """The single-pass segmented kernels (read at load: a fresh process): RLE_MI355X_SEG_RES=1, the
-    resident form (encode and decode; the segment edges at its segment length), and =2, the decode
-    without the resident segment (round 5: its write walk re-reads the segment): this whole module
-    again, plus the drop-in's large files, against the oracle."""
-    if RES_MODE != "0":
-        pytest.skip("already a single-pass run")
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ, RLE_MI355X_SEG_RES=mode, RLE_MI355X_LIB=_variants_lib(os.path.dirname(here)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
-                        os.path.join(here, "test_gpu_segmented.py"), "-k", "not fused and not resident"],
-                       env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])

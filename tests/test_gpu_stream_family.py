@@ -11,8 +11,7 @@ round and stream ends of each form:
   one wave, 192 chunks   decode_batch, n <= 4096
   one wave, 96 chunks    decode_batch, n >= 4097 (rle_kernels.hip decode_launch `large`)
   cooperative            set_coop_mode(1) + the batch's size hints; a later round past 16 tiles
-  segmented              decode_batch_seg, many buffers and one buffer (RLE_SEG_ONE); the resident
-                         single pass in a child process on the test library
+  segmented              decode_batch_seg, many buffers and one buffer (RLE_SEG_ONE)
   rounds                 set_dec_round(4 / 8 / 16), more than 4096 buffers
   drop-in                RLEdecompress with E = C + 16, RLEdecompressN (cap = U)
 
@@ -28,11 +27,9 @@ csrc/rle_device.h dec_serial (counts outside '2'..'9' -- '1' is never emitted as
 digit test declines it -- unbounded counts before the last token, or a decoded size past U); the
 kernels agreed with it as written, neither side was changed.  The round form decides per buffer in
 the same way and holds the same condition; the segmented form asserts serial-class => SERIAL only
-(a late look-back may add the bit, rle_segmented.hip)."""
+(its scan sends a whole buffer to the serial path when a taken phase declines in any segment)."""
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -44,8 +41,6 @@ from conftest import GOLDEN
 from test_gpu_parity import gpu_decode
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-RES = os.environ.get("RLE_MI355X_SEG_RES", "0") == "1"   # the child run of test_seg_resident_single_pass
 INFO = R.RLE_STATUS_OVERFLOW | R.RLE_STATUS_SERIAL | R.RLE_STATUS_SHORT
 
 with open(os.path.join(GOLDEN, "stream_family.json")) as _f:
@@ -124,17 +119,14 @@ def test_cooperative(group, always_coop):
 # ------------------------------------------------------------------ segmented
 def _seg_tiles(total):
     """The launcher's segment length in tiles: a mirror of rle_segmented.hip seg_bytes (about 16
-    segments per CU over the batch, 4..16 tiles; the resident single pass has 7-tile segments),
+    segments per CU over the batch, 4..16 tiles),
     checked against the library's own query (rle_seg_segment_bytes).  The tests below assert this
     mirror's value, so that they fail
     loudly -- rather than quietly test no segment edge -- if seg_bytes changes or the device has
     so few CUs (a partition of the chip) that these launch sizes give another segment length; such
     a failure asks for other launch sizes here, it is no decoder bug."""
-    if RES:
-        tiles = 7
-    else:
-        ncu = torch.cuda.get_device_properties(0).multi_processor_count
-        tiles = min(16, max(4, (total + F.TILE - 1) // F.TILE // (ncu * 16)))
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    tiles = min(16, max(4, (total + F.TILE - 1) // F.TILE // (ncu * 16)))
     assert R.seg_segment_bytes(total) == tiles * F.TILE, (total, tiles, R.seg_segment_bytes(total))
     return tiles
 
@@ -148,7 +140,7 @@ def _seg_decode_in_launches(cases, limit, want_tiles):
         while j < len(cases) and (j == i or total + len(cases[j].stream) <= limit):
             total += len(cases[j].stream)
             j += 1
-        assert RES or _seg_tiles(total) == want_tiles, (total, _seg_tiles(total))
+        assert _seg_tiles(total) == want_tiles, (total, _seg_tiles(total))
         d, s = decode(cases[i:j], seg=True)
         dec += d
         st += list(s)
@@ -156,13 +148,13 @@ def _seg_decode_in_launches(cases, limit, want_tiles):
     return dec, st
 
 
-SEG_S = F.SEG_RES if RES else F.SEG
+SEG_S = F.SEG
 
 
 def test_seg_small_launches():
     """Probes at S - 4 .. S + 2, 2 S - 4 .. 2 S + 2 and one tile past S (S = 64512, a multiple of
-    every segment length these launches take; 7056 in the resident run), in launches small enough
-    for the shortest segments (4 tiles): the summaries' serial bits and the look-back across the
+    every segment length these launches take), in launches small enough
+    for the shortest segments (4 tiles): the summaries' serial bits and the scan across the
     edge a bad or odd token sits on."""
     cases = F.cases(F.seg_positions(SEG_S))
     dec, st = _seg_decode_in_launches(cases, 12 << 20, 4)
@@ -173,7 +165,7 @@ def test_seg_one_launch():
     """The same cases in one launch, large enough for the longest segments (16 tiles)."""
     cases = F.cases(F.seg_positions(SEG_S))
     reps = 1
-    while not RES and _seg_tiles(reps * sum(len(c.stream) for c in cases)) < 16:
+    while _seg_tiles(reps * sum(len(c.stream) for c in cases)) < 16:
         reps += 1
     dec, st = decode(cases * reps, seg=True)
     n = len(cases)
@@ -201,21 +193,6 @@ def test_seg_one_buffer_launches():
         dec += d
         st += list(s)
     check(sample, dec, st, routing=False, pins=False)
-
-
-def test_seg_resident_single_pass():
-    """The resident single-pass segmented decode (RLE_MI355X_SEG_RES=1 on the test library, read at
-    load: a fresh process): the segmented tests of this module and of test_gpu_hostile_pad.py again,
-    with S = 7056."""
-    lib = os.path.join(os.path.dirname(HERE), "c-filestorage-server-and-client_amd", "build",
-                       "librle_mi355x_testhooks.so")
-    assert os.path.exists(lib), "build() makes the test library"
-    assert not RES
-    env = dict(os.environ, RLE_MI355X_SEG_RES="1", RLE_MI355X_LIB=lib)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider",
-                        os.path.join(HERE, "test_gpu_stream_family.py"), os.path.join(HERE, "test_gpu_hostile_pad.py"),
-                        "-k", "seg_ and not resident"], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and " passed" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
 
 
 # ------------------------------------------------------------------ rounds (opt-in)

@@ -54,15 +54,6 @@ CALLS = [
     ("reg_min=0", "compress 262145", 0, "large"),
     ("reg_min=0", "decompress 100000 262145 131071", 0, "mapped_seg"),
     ("fake_devs=2", "compress 262145", 0, "large"),
-    # the variants: coalescing takes every mapped call, the service those that are not segmented
-    ("coalesce=1", "compress 4096", 0, "mapped_coalesce"),
-    ("coalesce=1", "compress 100000", 0, "mapped_coalesce"),
-    ("coalesce=1", "decompress 100000 100000 0", 0, "mapped_coalesce"),
-    ("coalesce=1 zerocopy=0", "compress 4096", 0, "staged"),
-    ("service=1", "compress 4096", 0, "mapped_service"),
-    ("service=1", "compress 100000", 0, "mapped_seg"),
-    ("service=1", "decompress 4096 4096 0", 0, "mapped_service"),
-    ("service=1 coalesce=1", "decompress 4096 4096 0", 0, "mapped_coalesce"),
 ]
 
 # the kernels of a buffer in device memory: (call, segmented, output travels with its size)
